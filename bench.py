@@ -8,8 +8,15 @@ stride (rank g holds a[g::N]): local 2^20-point NTT + RCCL all-to-all + radix-N
 combine (DESIGN.md "Multi-GPU"), so per-GPU work is fixed (weak scaling).
 
 Prints ONE JSON line on rank 0 (contract in the task statement), including
-`roofline` (HBM-bound, algorithmic bytes 16*n per transform) and `cpu_baseline`
-(the oracle's recursion-faithful restatement of src/fft.rs:90-106, 1 core).
+`roofline` (HBM-bound, algorithmic bytes 16*n per transform, from the timed steps
+themselves).
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the
+outputs of the last timed step if `--dump-outputs DIR` is given, and the line. Everything
+that takes runs of its own is behind `--full`: `cpu_baseline` (the oracle's
+recursion-faithful restatement of src/fft.rs:90-106, 1 core), the live rocprofv3 traffic
+passes, and `extra` (the other sizes and configs, their CPU baselines, the sharded prove at
+N > 1). Under `--full`, `--no-cpu`, `--no-extra` and `--no-traffic` drop one of them each.
 """
 from __future__ import annotations
 
@@ -296,8 +303,14 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--log-n", type=int, default=20, help="per-GPU transform size (2^log_n)")
     ap.add_argument("--batch", type=int, default=32, help="polynomials per step")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the CPU baselines, the live rocprofv3 "
+                         "traffic passes and the side measurements in `extra` (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float64, see dump_outputs)")
     ap.add_argument("--cpu-budget", type=float, default=10.0, help="seconds of CPU baseline work")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-extra", action="store_true", help="skip the config 1/3/4 side measurements")
     ap.add_argument("--no-traffic", action="store_true", help="skip the live rocprofv3 PMC traffic passes")
     ap.add_argument("--prove-log-n", type=str, default="20,24",
@@ -307,6 +320,10 @@ def main() -> int:
                          "of the N > 1 code path on fewer GPUs than ranks (ranks share devices, device "
                          "buffers staged through the host; not a measurement)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: the headline only
+        args.no_cpu = args.no_extra = args.no_traffic = True
     global COLL_DEVICE
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -340,12 +357,14 @@ def main() -> int:
 
     if world == 1:
         step_fn, n_global = _single_gpu(ctx, n_local, B, sp)
+        last_output = step_fn.last_output
     else:
         from multigpu import BenchSharded, DistComm  # plonk-by-fingers_amd/multigpu.py
 
         sh = BenchSharded(ctx, dist if args.backend == "nccl" else DistComm(dist, world), rank, world, args.log_n, B,
                           sp)
         step_fn, n_global = sh.step, sh.n_global
+        last_output = lambda: sh.out  # noqa: E731  (this rank's shard of the result)
 
     for _ in range(args.warmup):
         step_fn()
@@ -369,6 +388,8 @@ def main() -> int:
     if dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall_max, ev_max = float(t[0]), float(t[1])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_output(), n_local)
 
     # config 5 across the ranks (BASELINE: "Full PLONK prove ... NTT sharded across 8xMI355X"),
     # after the headline timing so it cannot disturb it; every rank takes part
@@ -801,6 +822,37 @@ def other_configs(ctx, sp) -> dict:
     return res
 
 
+DUMP_SAMPLE = 1 << 21  # sampled elements in --dump-outputs (2 arrays x 8 B each: 32 MiB)
+DUMP_SEED = 0x5EED0D17
+
+
+def dump_outputs(out_dir: str, out: "torch.Tensor", n: int) -> None:
+    """Write the output of the last timed step (what a caller of ntt_batch_dev receives: B x n
+    Goldilocks elements in natural order, u64) as float64 .npy files. A u64 does not fit a
+    float64, so every value is written as its low and high 32-bit halves, each exact:
+      ntt_out_lo32.npy, ntt_out_hi32.npy: the elements at DUMP_SAMPLE fixed positions (numpy's
+        PCG64 seeded DUMP_SEED, without replacement, ascending; the whole output where it is no
+        larger than that);
+      ntt_out_sum_lo32.npy, ntt_out_sum_hi32.npy: the sums of the halves over every run of
+        min(n, 2^20) consecutive elements (< 2^52, so exact): a change anywhere in the output shows.
+    The inputs are seeded (splitmix64 0x5EED0002 + buffer set) and the buffer sets rotate per step,
+    so the same arguments give the same files from run to run."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    v = out.cpu().numpy().view(np.uint64)
+    lo = (v & np.uint64(0xFFFFFFFF)).astype(np.float64)
+    hi = (v >> np.uint64(32)).astype(np.float64)
+    if v.size > DUMP_SAMPLE:
+        idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(v.size, DUMP_SAMPLE, replace=False))
+    else:
+        idx = np.arange(v.size)
+    run = min(n, 1 << 20)
+    for name, a in (("ntt_out_lo32", lo[idx]), ("ntt_out_hi32", hi[idx]),
+                    ("ntt_out_sum_lo32", lo.reshape(-1, run).sum(axis=1)),
+                    ("ntt_out_sum_hi32", hi.reshape(-1, run).sum(axis=1))):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def _single_gpu(ctx, n, B, sp, sets: int = BUFFER_SETS):
     """One step = one batched forward NTT of B x n. Consecutive steps rotate over `sets`
     input/output buffer pairs (>= 3 sets, 3 x 512 MiB > the 256 MiB Infinity
@@ -818,6 +870,7 @@ def _single_gpu(ctx, n, B, sp, sets: int = BUFFER_SETS):
         k[0] += 1
         ctx.ntt_batch_dev(GOLD, w, buf_in.data_ptr(), buf_out.data_ptr(), n, B, stream=sp)
 
+    step.last_output = lambda: bufs[(k[0] - 1) % sets][1]  # the output buffer of the latest step
     return step, n
 
 
