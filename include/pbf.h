@@ -20,7 +20,8 @@
  *     also use streams private to the context, always joined back by events (waits in
  *     the command processor, never a spinning kernel) on the caller's stream before
  *     they return: a batched Goldilocks NTT of >= 8 polynomials
- *     (pbf_ntt_u64_batch_dev) forks half its groups onto a second stream, and the
+ *     (pbf_ntt_u64_batch_dev, pbf_ntt_u64_coset_batch_dev) forks half its groups onto a
+ *     second stream, and the
  *     fixed-base MSM (pbf_msm_g1_bn254_fixed_dev, and the commitments inside
  *     pbf_plonk_prove_bn254*) runs its bucket join and reduction on a side stream while
  *     the caller's stream goes on; the fixed-base MSM, prove and verify order the
@@ -107,6 +108,33 @@ int pbf_ntt_u64(pbf_ctx* ctx, uint64_t modulus, uint64_t omega, const uint64_t* 
 int pbf_ntt_u64_batch_dev(pbf_ctx* ctx, uint64_t modulus, uint64_t omega, const uint64_t* d_in,
                           uint64_t* d_out, size_t n, size_t batch, int inverse, void* stream);
 
+/* ---- coset NTT / low-degree extension ------------------------------------------
+ * The same transform on the coset shift * <omega> (the reference has none; its quotient,
+ * plonk.rs:339-370, is the caller that would want one: SURVEY.md §8(f)). modulus, omega and n
+ * as for pbf_ntt_u64 (omega of order exactly n).
+ *   inverse = 0: polynomial b is the in_len coefficients at in + b*in_len, compact, with
+ *     1 <= in_len <= n (any value: n/4 + 3 is legal), and
+ *       out[b*n + k] = sum_{j < in_len} in[b*in_len + j] * (shift * omega^k)^j,   natural order:
+ *     the low-degree extension with blow-up n / in_len. The zero padding is never stored or read.
+ *   inverse = 1: needs in_len == n (else PBF_EINVAL);
+ *       out[j] = shift^-j * n^-1 * sum_k in[k] * omega^(-j*k),
+ *     so inverse(forward(a)) == a bit for bit.
+ * shift must be canonical and non-zero; shift = 1 gives exactly pbf_ntt_u64*. shift = 0,
+ * shift >= modulus, in_len = 0 and in_len > n return PBF_EINVAL before anything is enqueued.
+ * Input and output may alias only when in_len == n. The host entry point checks its input
+ * canonical as pbf_ntt_u64 does. The _dev entry point follows the stream contract above; a
+ * batch of >= 8 Goldilocks polynomials forks half its groups onto the context's second stream,
+ * joined back by events before it returns, like pbf_ntt_u64_batch_dev. Standard-root
+ * Goldilocks transforms of n > 4096 apply the factors inside their first pass's loads
+ * (forward) or last pass's stores (inverse): no extra kernel or pass over the data. The
+ * context keeps the factor tables of the last 4 shifts used with each (modulus, omega, n,
+ * direction).                                                                            */
+int pbf_ntt_u64_coset(pbf_ctx* ctx, uint64_t modulus, uint64_t omega, uint64_t shift, const uint64_t* in,
+                      size_t in_len, uint64_t* out, size_t n, int inverse);
+int pbf_ntt_u64_coset_batch_dev(pbf_ctx* ctx, uint64_t modulus, uint64_t omega, uint64_t shift,
+                                const uint64_t* d_in, size_t in_len, uint64_t* d_out, size_t n, size_t batch,
+                                int inverse, void* stream);
+
 /* ---- mul_ntt ---------------------------------------------------------------- */
 /* fft.rs:109-132: zero-pad a (la) and b (lb) to la+lb (= the domain size, a power
  * of two), forward NTT both, multiply pointwise, inverse NTT. out has la+lb entries
@@ -169,6 +197,13 @@ int pbf_ntt_fr256(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* in, uint6
                   int inverse);
 int pbf_ntt_fr256_batch_dev(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* d_in, uint64_t* d_out,
                             size_t n, size_t batch, int inverse, void* stream);
+/* pbf_ntt_u64_coset* for Fr (shift: 4 x u64, canonical, non-zero): the same semantics, argument
+ * checks and aliasing rule; elements 4 x u64. A scaling kernel runs before the forward transform
+ * (which reads no zero padding) or after the inverse one.                                    */
+int pbf_ntt_fr256_coset(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* shift, const uint64_t* in,
+                        size_t in_len, uint64_t* out, size_t n, int inverse);
+int pbf_ntt_fr256_coset_batch_dev(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* shift, const uint64_t* d_in,
+                                  size_t in_len, uint64_t* d_out, size_t n, size_t batch, int inverse, void* stream);
 int pbf_mul_ntt_fr256(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* a, size_t la,
                       const uint64_t* b, size_t lb, uint64_t* out);
 /* batched device mul_ntt: a, b already zero-padded to n = la + lb; out = batch x n  */
@@ -258,8 +293,9 @@ int pbf_g2_bn254_mul(pbf_ctx* ctx, const uint64_t* pts, const uint64_t* scalars,
  * preprocessed commitments, plus device copies of the q / copies (and, for verify, SRS)
  * arrays they were built from (~0.2 KiB per gate each); every call compares its inputs
  * with those copies word for word and rebuilds on any difference. Outputs are identical
- * either way; PBF_PROVER_NO_PK=1 / PBF_VERIFIER_NO_VK=1 disable the keys, and
- * pbf_ctx_release_caches frees them (and the MSM window table) between circuits.        */
+ * either way; the context options prover.pk = 0 / verifier.vk = 0 (pbf_ctx_set_option)
+ * disable the keys, and pbf_ctx_release_caches frees them (and the MSM window table)
+ * between circuits.                                                                     */
 int pbf_plonk_prove_bn254(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies, const uint64_t* abc,
                           const uint64_t* chal, const uint64_t* rnd, const uint64_t* k1k2, const uint64_t* srs,
                           size_t srs_m, int mode, uint64_t* out_pts, uint64_t* out_f);

@@ -188,6 +188,53 @@ int pbf_ntt_u64_batch_dev(pbf_ctx* ctx, uint64_t modulus, uint64_t omega, const 
   return run_plan(*p, d_in, d_out, batch, ctx->scratch0, ctx->scratch1, ctx->pick(stream), &ctx->fork);
 }
 
+// Argument checks shared by the coset entry points (include/pbf.h): nothing is enqueued on failure
+static int coset_check(uint64_t modulus, uint64_t shift, size_t in_len, size_t n, int inverse) {
+  if (shift == 0 || shift >= modulus) return fail(PBF_EINVAL, "shift must be canonical and non-zero");
+  if (in_len == 0 || in_len > n) return fail(PBF_EINVAL, "in_len must be in 1..n");
+  if (inverse && in_len != n) return fail(PBF_EINVAL, "the inverse coset transform needs in_len == n");
+  return 0;
+}
+
+// The FFT trait's transform on the coset shift * <omega>: the low-degree extension of in_len
+// coefficients to n evaluations, and its inverse (no counterpart in the reference, whose
+// quotient at plonk.rs:339-370 would run on such a coset: SURVEY §8(f))
+int pbf_ntt_u64_coset(pbf_ctx* ctx, uint64_t modulus, uint64_t omega, uint64_t shift, const uint64_t* in,
+                      size_t in_len, uint64_t* out, size_t n, int inverse) {
+  if (!ctx || !in || !out) return fail(PBF_EINVAL, "null argument");
+  int rc = coset_check(modulus, shift, in_len, n, inverse);
+  if (rc) return rc;
+  NttPlan* p;
+  if ((rc = ctx->plan(modulus, omega, n, inverse, &p))) return rc;
+  if (!all_canonical(in, in_len, modulus)) return fail(PBF_EINVAL, "input not canonical");
+  hipStream_t s = ctx->host_stream();
+  if ((rc = ctx->io0.ensure(n * 8))) return rc;
+  uint64_t* d_out = (uint64_t*)ctx->io0.p;
+  uint64_t* d_in = d_out;  // in place when the input is a whole polynomial
+  if (in_len < n) {
+    if ((rc = ctx->io1.ensure(in_len * 8))) return rc;
+    d_in = (uint64_t*)ctx->io1.p;
+  }
+  PBF_HIP(hipMemcpyAsync(d_in, in, in_len * 8, hipMemcpyHostToDevice, s));
+  if ((rc = run_plan_coset(*p, shift, d_in, in_len, d_out, 1, ctx->scratch0, ctx->scratch1, s))) return rc;
+  PBF_HIP(hipMemcpyAsync(out, d_out, n * 8, hipMemcpyDeviceToHost, s));
+  PBF_HIP(hipStreamSynchronize(s));
+  return PBF_OK;
+}
+
+int pbf_ntt_u64_coset_batch_dev(pbf_ctx* ctx, uint64_t modulus, uint64_t omega, uint64_t shift, const uint64_t* d_in,
+                                size_t in_len, uint64_t* d_out, size_t n, size_t batch, int inverse, void* stream) {
+  if (!ctx || !d_in || !d_out) return fail(PBF_EINVAL, "null argument");
+  int rc = coset_check(modulus, shift, in_len, n, inverse);
+  if (rc) return rc;
+  if (d_in == d_out && in_len != n) return fail(PBF_EINVAL, "input and output may alias only when in_len == n");
+  NttPlan* p;
+  if ((rc = ctx->plan(modulus, omega, n, inverse, &p))) return rc;
+  PBF_HIP(hipSetDevice(ctx->device));
+  return run_plan_coset(*p, shift, d_in, in_len, d_out, batch, ctx->scratch0, ctx->scratch1, ctx->pick(stream),
+                        &ctx->fork);
+}
+
 // fft.rs:109-132 mul_ntt
 int pbf_mul_ntt_u64(pbf_ctx* ctx, uint64_t modulus, uint64_t omega, const uint64_t* a, size_t la, const uint64_t* b,
                     size_t lb, uint64_t* out) {

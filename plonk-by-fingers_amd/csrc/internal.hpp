@@ -94,6 +94,20 @@ struct DevBuf {
   ~DevBuf();
 };
 
+// Coset factor table of one (plan, shift) (ntt_launch.hip coset_tabs): entry i = c s^i for
+// i < len, with s = shift, c = 1 for a forward plan and s = shift^-1 for an inverse one (c = n^-1
+// where the plan's passes are ntt_gl_pass_kernel's, whose last pass then applies it: CS 2; the
+// regrouped 2^24 plan keeps n^-1 in its own last-pass table, so c = 1 there).
+// Laid out like a polynomial and shared by a whole batch. One level (t1 empty) up to
+// 2^ntt.twmax_log entries; above, s^i = t0[i mod 2^bits] * t1[i >> bits] with c in t0.
+struct CosetTabs {
+  uint64_t shift = 0, len = 0, stamp = 0;
+  uint32_t bits = 0;
+  DevBuf t0, t1;
+  DevBuf tc_last;  // Goldilocks inverse plans: the last pass's stage-C table without n^-1
+};
+constexpr size_t COSET_SHIFTS_PER_PLAN = 4;
+
 // A planned NTT: (modulus, omega, n, direction) -> passes + device twiddle tables.
 struct NttPlan {
   uint64_t m = 0, omega = 0, n = 0;
@@ -125,6 +139,10 @@ struct NttPlan {
   mutable bool rg_built = false;
   mutable DevBuf rg_tc1, rg_t2;
   mutable DevBuf rg_tgc, rg_tgb;
+  // coset transforms (run_plan_coset): the factor tables of the last COSET_SHIFTS_PER_PLAN
+  // shifts used with this plan, least recently used evicted, freed with the plan
+  mutable std::vector<std::unique_ptr<CosetTabs>> coset;
+  mutable uint64_t coset_clock = 0;
 };
 
 // Extra streams and events of the multi-stream NTT group schedule (ntt_launch.hip
@@ -173,6 +191,13 @@ int make_plan(uint64_t m, uint64_t omega, uint64_t n, int inverse, NttPlan* p);
 // Goldilocks batches; null keeps every launch on `stream`.
 int run_plan(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out, size_t batch, DevBuf& s0, DevBuf& s1,
              hipStream_t stream, ForkSet* fork = nullptr);
+// The same transform on the coset shift * <omega> (include/pbf.h pbf_ntt_u64_coset*). Forward:
+// polynomial b is the in_len <= n coefficients at d_in + b*in_len, out[k] = sum_j in[j] (shift
+// omega^k)^j. Inverse (in_len = n): the plain inverse times shift^-j. Standard-root Goldilocks
+// plans fuse the factor into the first pass's loads / the last pass's stores; the others run a
+// scaling kernel before / after the plain transform.
+int run_plan_coset(const NttPlan& p, uint64_t shift, const uint64_t* d_in, size_t in_len, uint64_t* d_out,
+                   size_t batch, DevBuf& s0, DevBuf& s1, hipStream_t stream, ForkSet* fork = nullptr);
 // Kernel launchers (ntt_launch.hip)
 int launch_pointwise_mul(FieldKind k, const FieldArgs& fa, const uint64_t* a, const uint64_t* b, uint64_t* c,
                          uint64_t count, hipStream_t s);

@@ -981,7 +981,74 @@ int pbf_internal_ntt_fr256_prefix(pbf_ctx* ctx, const uint64_t* omega, uint64_t*
   return run256(*p, (const U256*)d_io, (U256*)d_io, batch, ctx->scratch0, ctx->scratch1, s, nullptr, in_len);
 }
 
+namespace pbf {
+int fr256_scale_pow(bool l29, const uint64_t* in, uint64_t len, uint64_t* out, uint64_t out_pitch, uint64_t batch,
+                    const U256& base, hipStream_t s);  // prover.hip
+}
+
+// The Fr coset transforms (include/pbf.h pbf_ntt_fr256_coset*): the prover's scaling kernel and
+// prefix transform behind a public interface. Forward: out[b] = NTT(in[b][j] shift^j, zero-padded
+// to n); inverse: the plain inverse times shift^-j.
+static int fr256_coset_check(const uint64_t* shift, size_t in_len, size_t n, int inverse, U256* sm) {
+  const U256 sh = h_from64(shift);
+  if (!h_canonical(sh) || !(shift[0] | shift[1] | shift[2] | shift[3]))
+    return fail(PBF_EINVAL, "shift must be canonical and non-zero");
+  if (in_len == 0 || in_len > n) return fail(PBF_EINVAL, "in_len must be in 1..n");
+  if (inverse && in_len != n) return fail(PBF_EINVAL, "the inverse coset transform needs in_len == n");
+  *sm = Fr::to_mont(sh);
+  return 0;
+}
+
+static int fr256_coset_run(pbf_ctx* ctx, const uint64_t* omega, const U256& sm, const uint64_t* d_in, size_t in_len,
+                           uint64_t* d_out, size_t n, size_t batch, int inverse, hipStream_t s) {
+  Plan256* p;
+  int rc = get_plan256(ctx, omega, n, inverse, &p);
+  if (rc) return rc;
+  PBF_HIP(hipSetDevice(ctx->device));
+  const bool l29 = ctx->options.num("ntt256.l29", 1) != 0;
+  if (inverse) {
+    if ((rc = run256(*p, (const U256*)d_in, (U256*)d_out, batch, ctx->scratch0, ctx->scratch1, s))) return rc;
+    return fr256_scale_pow(l29, d_out, n, d_out, n, batch, h_inv(sm), s);
+  }
+  if ((rc = fr256_scale_pow(l29, d_in, in_len, d_out, n, batch, sm, s))) return rc;
+  return pbf_internal_ntt_fr256_prefix(ctx, omega, d_out, n, batch, in_len, s);
+}
+
 extern "C" {
+
+int pbf_ntt_fr256_coset(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* shift, const uint64_t* in, size_t in_len,
+                        uint64_t* out, size_t n, int inverse) {
+  if (!ctx || !omega || !shift || !in || !out) return fail(PBF_EINVAL, "null argument");
+  U256 sm;
+  int rc = fr256_coset_check(shift, in_len, n, inverse, &sm);
+  if (rc) return rc;
+  Plan256* p;
+  if ((rc = get_plan256(ctx, omega, n, inverse, &p))) return rc;
+  if (!canonical_vec(in, in_len)) return fail(PBF_EINVAL, "input not canonical");
+  hipStream_t s = ctx->host_stream();
+  if ((rc = ctx->io0.ensure(n * 32))) return rc;
+  uint64_t* d_out = (uint64_t*)ctx->io0.p;
+  uint64_t* d_in = d_out;  // in place when the input is a whole polynomial
+  if (in_len < n) {
+    if ((rc = ctx->io1.ensure(in_len * 32))) return rc;
+    d_in = (uint64_t*)ctx->io1.p;
+  }
+  PBF_HIP(hipMemcpyAsync(d_in, in, in_len * 32, hipMemcpyHostToDevice, s));
+  if ((rc = fr256_coset_run(ctx, omega, sm, d_in, in_len, d_out, n, 1, inverse, s))) return rc;
+  PBF_HIP(hipMemcpyAsync(out, d_out, n * 32, hipMemcpyDeviceToHost, s));
+  PBF_HIP(hipStreamSynchronize(s));
+  return PBF_OK;
+}
+
+int pbf_ntt_fr256_coset_batch_dev(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* shift, const uint64_t* d_in,
+                                  size_t in_len, uint64_t* d_out, size_t n, size_t batch, int inverse, void* stream) {
+  if (!ctx || !omega || !shift || !d_in || !d_out) return fail(PBF_EINVAL, "null argument");
+  U256 sm;
+  int rc = fr256_coset_check(shift, in_len, n, inverse, &sm);
+  if (rc) return rc;
+  if (d_in == d_out && in_len != n) return fail(PBF_EINVAL, "input and output may alias only when in_len == n");
+  return fr256_coset_run(ctx, omega, sm, d_in, in_len, d_out, n, batch, inverse, (hipStream_t)stream);
+}
 
 // fft.rs:109-132 mul_ntt for BN254 Fr; out has la+lb elements (4 x u64 each)
 int pbf_mul_ntt_fr256(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* a, size_t la, const uint64_t* b,

@@ -72,6 +72,16 @@ struct GlPassArgs {
   // second pass skips its own (skip_pass_tw)
   const uint64_t* post_tw;
   uint32_t skip_pass_tw;
+  // coset variants (template parameter CS of the kernel). CS 1, the first pass
+  // of a forward transform: polynomial `poly` is the cs_len coefficients at in + poly*in_pitch
+  // (in_pitch = cs_len), element i loads times shift^i, and i >= cs_len is zero padding that is
+  // never read. CS 2, the last pass of an inverse: output k stores times shift^-k n^-1 (tc
+  // unscaled). The factor of index i is cs_tab[i], or, two-level (cs_tab1 != null),
+  // cs_tab[i mod 2^cs_bits] * cs_tab1[i >> cs_bits].
+  const uint64_t* cs_tab;
+  const uint64_t* cs_tab1;
+  uint32_t cs_bits;
+  uint64_t cs_len;
 };
 
 // x * 2^(K mod 192) (mod p), K a compile-time exponent; 2^96 = -1. Exponents in
@@ -181,17 +191,27 @@ __device__ __forceinline__ void gl_tile_coords(const GlPassArgs& a, uint32_t til
   }
 }
 
+// coset factor of element i (GlPassArgs cs_tab)
+__device__ __forceinline__ uint64_t gl_cs_factor(const GlPassArgs& a, uint64_t i) {
+  const FieldArgs f{};
+  if (a.cs_tab1) return Goldilocks::mul(a.cs_tab[i & ((1ull << a.cs_bits) - 1)], a.cs_tab1[i >> a.cs_bits], f);
+  return a.cs_tab[i];
+}
+
 constexpr int GL_STORES = 16;  // global stores per thread per tile (NSUB_C * C)
 
 // One tile: stages A, B, C and the stores.
 // RG (regrouped 2^24 plan, ntt_gl_rg2_kernel below): 1 = its first pass, 3 = its last pass.
-template <int LOGR, int E64, bool FIRST, int TILE, int RG = 0>
+// CS (coset transforms): 1 = a first pass that scales its loads by shift^i and reads no zero
+// padding, 2 = a last pass that scales its stores by shift^-k n^-1 (GlPassArgs cs_*).
+template <int LOGR, int E64, bool FIRST, int TILE, int RG = 0, int CS = 0>
 __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint32_t tile, uint32_t tiles, int t) {
   using Sh = GlShape<LOGR, TILE>;
   constexpr int C = Sh::C, LOGC = Sh::LOGC, W = Sh::W, NT = Sh::NT, YP = Sh::YP;
   (void)YP;
   static_assert(Sh::NSUB_C * C == GL_STORES, "stores per thread");
   static_assert(RG == 0 || (LOGR == 8 && TILE == 4096 && FIRST == (RG == 1)), "RG shape");
+  static_assert(CS == 0 || (FIRST == (CS == 1) && (RG == 0 || RG == 2 * CS - 1)), "CS 1: first pass, CS 2: last pass");
   const FieldArgs f{};
   using G = Goldilocks;
   uint32_t poly, kb;
@@ -203,14 +223,37 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
 
   // ---------------- stage A: load, pass twiddle, 4-point DFTs over s1
   uint64_t v[16];
+  if constexpr (CS == 1) {
+    // in groups of 8 elements like the pass twiddle below: a group's data and factor loads
+    // issue together; an element past the coefficients is 0 and loads neither
 #pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int idx = t + NT * u;
-    const int w = idx % W, r2 = (idx / W) % C, s2 = idx / (C * W);
+    for (int h = 0; h < 2; ++h) {
+      uint64_t tw[8];
 #pragma unroll
-    for (int s1 = 0; s1 < 4; ++s1) {
-      const int r = 16 * C * s1 + C * s2 + r2;
-      v[u * 4 + s1] = in[(j0 + w) + (uint64_t)r * stride];
+      for (int uu = 0; uu < 2; ++uu) {
+        const int idx = t + NT * (2 * h + uu);
+        const int w = idx % W, r2 = (idx / W) % C, s2 = idx / (C * W);
+#pragma unroll
+        for (int s1 = 0; s1 < 4; ++s1) {
+          const uint64_t i = (j0 + w) + (uint64_t)(16 * C * s1 + C * s2 + r2) * stride;
+          const bool on = i < a.cs_len;
+          v[8 * h + uu * 4 + s1] = on ? in[i] : 0;
+          tw[uu * 4 + s1] = on ? gl_cs_factor(a, i) : 0;
+        }
+      }
+#pragma unroll
+      for (int m = 0; m < 8; ++m) v[8 * h + m] = G::mul(v[8 * h + m], tw[m], f);
+    }
+  } else {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int idx = t + NT * u;
+      const int w = idx % W, r2 = (idx / W) % C, s2 = idx / (C * W);
+#pragma unroll
+      for (int s1 = 0; s1 < 4; ++s1) {
+        const int r = 16 * C * s1 + C * s2 + r2;
+        v[u * 4 + s1] = in[(j0 + w) + (uint64_t)r * stride];
+      }
     }
   }
   // RG 3: the stage-B general twiddle w^(a0 X) (a0 = r2 + 4 s2, X = 65536 q1 + j), geometric in
@@ -409,6 +452,13 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
       const uint64_t j = j0 + w;
       const uint64_t base = ((j >> a.log_ns) << (a.log_ns + LOGR)) + (j & ns_mask);
       if (sl == 0) {
+        if constexpr (CS == 2) {
+          uint64_t tw[C];
+#pragma unroll
+          for (int k2 = 0; k2 < C; ++k2) tw[k2] = gl_cs_factor(a, base + ((uint64_t)(k1 + 64 * k2) << a.log_ns));
+#pragma unroll
+          for (int k2 = 0; k2 < C; ++k2) x[u * C + bitrev_c(k2, LOGC)] = G::mul(x[u * C + bitrev_c(k2, LOGC)], tw[k2], f);
+        }
 #pragma unroll
         for (int k2 = 0; k2 < C; ++k2)
           if (!PBF_GL_NOMEM_ON || x[u * C + bitrev_c(k2, LOGC)] == 0x123456789ull)
@@ -434,7 +484,7 @@ __device__ __forceinline__ void gl_shape_checks() {
 }
 
 // One tile per workgroup.
-template <int LOGR, int E64, bool FIRST, int TILE, int RG = 0>
+template <int LOGR, int E64, bool FIRST, int TILE, int RG = 0, int CS = 0>
 // waves per SIMD the VGPR budget allows: 5 where the LDS allows five workgroups and the
 // kernel fits 96 VGPRs without spilling (first passes and the regrouped plan's), else 4
 __global__ void __launch_bounds__(TILE / 16)
@@ -443,7 +493,7 @@ ntt_gl_pass_kernel(GlPassArgs a) {
   gl_shape_checks<LOGR, TILE>();
   __shared__ __attribute__((aligned(16))) uint64_t lds[GlShape<LOGR, TILE>::LDS];
   const uint32_t tiles = a.blocks_per_poly * a.batch;
-  gl_tile<LOGR, E64, FIRST, TILE, RG>(a, lds, blockIdx.x, tiles, threadIdx.x);
+  gl_tile<LOGR, E64, FIRST, TILE, RG, CS>(a, lds, blockIdx.x, tiles, threadIdx.x);
 }
 
 // ---- regrouped 2^24 plan (DESIGN.md §3.1 "Regrouped twiddles") --------------------------

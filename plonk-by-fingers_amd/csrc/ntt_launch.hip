@@ -260,8 +260,16 @@ static PassFn pass_fn(FieldKind k, int e64, int logr, PassCfg c) {
   return pass_fn_e<Goldilocks, -1>(logr, c);
 }
 
+// A coset transform on the ntt_gl_pass_kernel passes (run_plan_coset): the factor table and,
+// forward, the compact input's length
+struct GlCoset {
+  const CosetTabs* tabs;
+  uint64_t in_len;
+};
+
 static int run_plan_impl(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out, size_t batch, DevBuf& s0,
-                         DevBuf& s1, hipStream_t stream, uint32_t split_log, ForkSet* fork = nullptr);
+                         DevBuf& s1, hipStream_t stream, uint32_t split_log, ForkSet* fork = nullptr,
+                         const GlCoset* cs = nullptr);
 
 int run_plan(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out, size_t batch, DevBuf& s0, DevBuf& s1,
              hipStream_t stream, ForkSet* fork) {
@@ -376,6 +384,19 @@ static GlPassFn gl_fn_e(int logr, bool first) {
   }
 }
 
+// coset variants (ntt_gl.hpp CS): 1 = first pass scaling its loads, 2 = last pass scaling its stores
+template <int E>
+static GlPassFn gl_fn_cs(int logr, int cs) {
+  switch (logr) {
+    case 6: return cs == 1 ? ntt_gl_pass_kernel<6, E, true, 4096, 0, 1> : ntt_gl_pass_kernel<6, E, false, 4096, 0, 2>;
+    case 7: return cs == 1 ? ntt_gl_pass_kernel<7, E, true, 4096, 0, 1> : ntt_gl_pass_kernel<7, E, false, 4096, 0, 2>;
+    case 8: return cs == 1 ? ntt_gl_pass_kernel<8, E, true, 4096, 0, 1> : ntt_gl_pass_kernel<8, E, false, 4096, 0, 2>;
+    case 9: return cs == 1 ? ntt_gl_pass_kernel<9, E, true, 4096, 0, 1> : ntt_gl_pass_kernel<9, E, false, 4096, 0, 2>;
+    case 10: return cs == 1 ? ntt_gl_pass_kernel<10, E, true, 8192, 0, 1> : ntt_gl_pass_kernel<10, E, false, 8192, 0, 2>;
+    default: return nullptr;
+  }
+}
+
 // the regrouped 2^24 plan's three pass kernels
 template <int E>
 static GlPassFn gl_fn_rg(int pass) {
@@ -383,10 +404,16 @@ static GlPassFn gl_fn_rg(int pass) {
   if (pass == 1) return ntt_gl_rg2_kernel<E>;
   return ntt_gl_pass_kernel<8, E, false, 4096, 3>;
 }
+// and its first / last pass as coset variants (cs 1 / 2)
+template <int E>
+static GlPassFn gl_fn_rg_cs(int cs) {
+  return cs == 1 ? ntt_gl_pass_kernel<8, E, true, 4096, 1, 1> : ntt_gl_pass_kernel<8, E, false, 4096, 3, 2>;
+}
 
 // Passes of a standard-root Goldilocks plan through ntt_gl_pass_kernel (ntt_gl.hpp).
 static int run_gl_group(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out, size_t batch, DevBuf& s0,
-                        DevBuf& s1, hipStream_t stream, uint32_t split_log, size_t soff = 0);
+                        DevBuf& s1, hipStream_t stream, uint32_t split_log, size_t soff = 0,
+                        const GlCoset* cs = nullptr);
 
 int ForkSet::ensure(int streams) {
   if (streams > GL_MAX_STREAMS) streams = GL_MAX_STREAMS;
@@ -411,14 +438,17 @@ ForkSet::~ForkSet() {
 }
 
 static int run_gl_passes(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out, size_t batch, DevBuf& s0,
-                         DevBuf& s1, hipStream_t stream, uint32_t split_log, ForkSet* fork) {
+                         DevBuf& s1, hipStream_t stream, uint32_t split_log, ForkSet* fork, const GlCoset* cs) {
   // default schedule (measured best at 2^20 x 32): groups of 4 polynomials
   // alternating over the caller's stream and a second one once the batch has at least 8, so the
   // passes of two groups run concurrently and their load / compute / store phases interleave
   // (options ntt.group = polynomials per group, ntt.streams = streams; 0 or >= batch: one group)
   const long long go = p.opts.num("ntt.group", -1);
   const size_t G = go >= 0 ? (size_t)go : (batch >= 8 ? 4 : batch);
-  if (split_log != 0 || G == 0 || G >= batch) return run_gl_group(p, d_in, d_out, batch, s0, s1, stream, split_log);
+  if (split_log != 0 || G == 0 || G >= batch)
+    return run_gl_group(p, d_in, d_out, batch, s0, s1, stream, split_log, 0, cs);
+  // a forward coset transform reads compact polynomials of in_len coefficients
+  const size_t in_pitch = (cs && !p.inverse) ? cs->in_len : p.n;
   int ns = (int)p.opts.num("ntt.streams", 2);
   ns = ns < 1 ? 1 : (ns > GL_MAX_STREAMS ? GL_MAX_STREAMS : ns);
   if (!fork) ns = 1;
@@ -439,8 +469,8 @@ static int run_gl_passes(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out
   int gi = 0;
   for (size_t g0 = 0; g0 < batch; g0 += G, ++gi) {
     const size_t b = batch - g0 < G ? batch - g0 : G;
-    const int rc = run_gl_group(p, d_in + g0 * p.n, d_out + g0 * p.n, b, s0, s1, sts[gi % ns], 0,
-                                ns > 1 ? g0 * p.n : 0);
+    const int rc = run_gl_group(p, d_in + g0 * in_pitch, d_out + g0 * p.n, b, s0, s1, sts[gi % ns], 0,
+                                ns > 1 ? g0 * p.n : 0, cs);
     if (rc) return rc;
   }
   for (int i = 1; i < ns; ++i) {
@@ -498,9 +528,10 @@ static int ensure_rg_tables(const NttPlan& p) {
 }
 
 static int run_gl_group(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out, size_t batch, DevBuf& s0,
-                        DevBuf& s1, hipStream_t stream, uint32_t split_log, size_t soff) {
+                        DevBuf& s1, hipStream_t stream, uint32_t split_log, size_t soff, const GlCoset* cs) {
   const size_t P = p.logr.size();
   const bool rg = p.rg && P == 3 && split_log == 0;
+  if (cs && (split_log != 0 || P < 2)) return fail(1, "coset transform: unsupported plan");
   if (rg) {
     const int rc = ensure_rg_tables(p);
     if (rc) return rc;
@@ -511,6 +542,10 @@ static int run_gl_group(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out,
     const int tile = gl_tile(lr);
     GlPassFn fn = p.e64 == 39 ? gl_fn_e<39>(lr, log_ns == 0) : gl_fn_e<153>(lr, log_ns == 0);
     if (rg) fn = p.e64 == 39 ? gl_fn_rg<39>((int)i) : gl_fn_rg<153>((int)i);
+    // coset: a forward transform's first pass scales its loads, an inverse's last pass its stores
+    const int csv = !cs ? 0 : (!p.inverse && i == 0) ? 1 : (p.inverse && i == P - 1) ? 2 : 0;
+    if (csv && rg) fn = p.e64 == 39 ? gl_fn_rg_cs<39>(csv) : gl_fn_rg_cs<153>(csv);
+    else if (csv) fn = p.e64 == 39 ? gl_fn_cs<39>(lr, csv) : gl_fn_cs<153>(lr, csv);
     if (!fn) return fail(1, "no Goldilocks pass kernel for this radix");
     const uint64_t W = (uint64_t)tile >> lr;
     if ((p.n >> lr) % W) return fail(1, "transform too small for the pass tile");
@@ -549,6 +584,21 @@ static int run_gl_group(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out,
       else a.skip_pass_tw = 1;
     }
     if (a.post_tw && batch > 1 && tiles % 8 == 0) a.xcd_kmajor = 1;
+    a.cs_tab = a.cs_tab1 = nullptr;
+    a.cs_bits = 0;
+    a.cs_len = 0;
+    if (csv) {
+      a.cs_tab = (const uint64_t*)cs->tabs->t0.p;
+      a.cs_tab1 = (const uint64_t*)cs->tabs->t1.p;
+      a.cs_bits = cs->tabs->bits;
+      if (csv == 1) {
+        a.cs_len = cs->in_len;
+        a.in_pitch = cs->in_len;
+      } else if (!rg) {
+        a.tc = (const uint64_t*)cs->tabs->tc_last.p;  // n^-1 rides in the factor table
+        a.scaled = 0;
+      }  // (the regrouped plan's last pass keeps n^-1 in its own table: ensure_rg_tables)
+    }
     if (rg) {
       if (i == 0) a.tc = (const uint64_t*)p.rg_tc1.p;
       if (i == 1) a.twpass = (const uint64_t*)p.rg_t2.p;
@@ -570,7 +620,7 @@ static int run_gl_group(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out,
 }
 
 static int run_plan_impl(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out, size_t batch, DevBuf& s0,
-                         DevBuf& s1, hipStream_t stream, uint32_t split_log, ForkSet* fork) {
+                         DevBuf& s1, hipStream_t stream, uint32_t split_log, ForkSet* fork, const GlCoset* cs) {
   if (batch == 0) return 0;
   if (p.n == 1) {
     if (d_in != d_out) PBF_HIP(hipMemcpyAsync(d_out, d_in, batch * 8, hipMemcpyDeviceToDevice, stream));
@@ -592,7 +642,8 @@ static int run_plan_impl(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out
   if (!rc && P > 2) rc = s1.ensure(bytes);
   if (rc) return rc;
   uint32_t log_ns = 0;
-  if (p.gl) return run_gl_passes(p, d_in, d_out, batch, s0, s1, stream, split_log, fork);
+  if (p.gl) return run_gl_passes(p, d_in, d_out, batch, s0, s1, stream, split_log, fork, cs);
+  if (cs) return fail(1, "coset transform: not a Goldilocks standard-root plan");
   for (size_t i = 0; i < P; ++i) {
     const int lr = p.logr[i];
     PassCfg cfg = pass_cfg(lr);
@@ -633,6 +684,132 @@ static int run_plan_impl(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out
     log_ns += lr;
   }
   return 0;
+}
+
+// ---------------------------------------------------------------- coset transforms
+static uint32_t log2_ceil(uint64_t x) {
+  uint32_t l = 0;
+  while ((1ull << l) < x) ++l;
+  return l;
+}
+
+// The factor table of (plan, shift) with at least `len` entries (internal.hpp CosetTabs), from
+// the plan's cache or built on the host like make_plan's tables. An evicted table is freed by
+// hipFree, which waits for the kernels still reading it; a forward table that a longer input
+// outgrows is rebuilt after a device synchronisation.
+static int coset_tabs(const NttPlan& p, uint64_t shift, uint64_t len, const CosetTabs** out) {
+  const uint64_t m = p.m;
+  CosetTabs* t = nullptr;
+  for (auto& c : p.coset)
+    if (c->shift == shift) t = c.get();
+  if (t && t->len >= len) {
+    t->stamp = ++p.coset_clock;
+    *out = t;
+    return 0;
+  }
+  if (!t) {
+    if (p.coset.size() >= COSET_SHIFTS_PER_PLAN) {
+      size_t old = 0;
+      for (size_t i = 1; i < p.coset.size(); ++i)
+        if (p.coset[i]->stamp < p.coset[old]->stamp) old = i;
+      p.coset.erase(p.coset.begin() + old);
+    }
+    p.coset.emplace_back(new CosetTabs());
+    t = p.coset.back().get();
+    t->shift = shift;
+  } else {
+    PBF_HIP(hipDeviceSynchronize());  // rebuilt longer, in place: no kernel may still read it
+  }
+  t->len = 0;  // not valid until every upload below has succeeded
+  uint64_t s = shift, c = 1 % m;
+  if (p.inverse) {
+    if (!hinv(shift, m, &s)) return fail(1, "shift has no inverse");
+    if (p.gl && !p.rg) c = p.n_inv;
+  }
+  long long tm = p.opts.num("ntt.twmax_log", 24);
+  const int twmax = (int)(tm < 0 ? 0 : (tm > 30 ? 30 : tm));
+  int rc;
+  if (len <= (1ull << twmax)) {
+    std::vector<uint64_t> v(len);
+    uint64_t x = c;
+    for (uint64_t i = 0; i < len; ++i) { v[i] = x; x = hmul(x, s, m); }
+    t->bits = 0;
+    t->t1.release();
+    if ((rc = upload(t->t0, v))) return rc;
+  } else {
+    t->bits = (log2_ceil(len) + 1) / 2;
+    std::vector<uint64_t> v0(1ull << t->bits), v1(((len - 1) >> t->bits) + 1);
+    uint64_t x = c, y = 1 % m;
+    for (size_t i = 0; i < v0.size(); ++i) { v0[i] = x; x = hmul(x, s, m); }
+    const uint64_t step = hpow(s, 1ull << t->bits, m);
+    for (size_t i = 0; i < v1.size(); ++i) { v1[i] = y; y = hmul(y, step, m); }
+    if ((rc = upload(t->t0, v0)) || (rc = upload(t->t1, v1))) return rc;
+  }
+  if (p.gl && !p.rg && p.inverse && !t->tc_last.p) {
+    const uint64_t R = 1ull << p.logr.back(), C = R / 64;
+    uint64_t w;
+    if (!hinv(p.omega, m, &w)) return fail(1, "omega not invertible");
+    const uint64_t wr = hpow(w, p.n / R, m);
+    std::vector<uint64_t> tc(C * 64);
+    for (uint64_t r2 = 0; r2 < C; ++r2)
+      for (uint64_t k1 = 0; k1 < 64; ++k1) tc[r2 * 64 + k1] = hpow(wr, r2 * k1, m);
+    if ((rc = upload(t->tc_last, tc))) return rc;
+  }
+  t->len = len;
+  t->stamp = ++p.coset_clock;
+  *out = t;
+  return 0;
+}
+
+// out[b*n + i] = i < in_len ? in[b*in_len + i] * factor(i) : 0 (the scaling pass of the plans
+// that do not fuse it; in may equal out when in_len = n)
+template <class F>
+__global__ void coset_scale_kernel(const uint64_t* in, uint64_t in_len, uint64_t* out, uint64_t n, uint64_t batch,
+                                   const uint64_t* t0, const uint64_t* t1, uint32_t bits, FieldArgs f) {
+  const uint64_t total = n * batch;
+  for (uint64_t id = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; id < total;
+       id += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t b = id / n, i = id % n;
+    uint64_t y = 0;
+    if (i < in_len) {
+      const uint64_t tw = t1 ? F::mul(t0[i & ((1ull << bits) - 1)], t1[i >> bits], f) : t0[i];
+      y = F::mul(in[b * in_len + i], tw, f);
+    }
+    out[id] = y;
+  }
+}
+
+static int launch_coset_scale(const NttPlan& p, const CosetTabs& t, const uint64_t* in, uint64_t in_len, uint64_t* out,
+                              uint64_t batch, hipStream_t s) {
+  const dim3 grid((uint32_t)grid_for(p.n * batch));
+  if (p.kind == FIELD_GOLDILOCKS)
+    hipLaunchKernelGGL(coset_scale_kernel<Goldilocks>, grid, dim3(256), 0, s, in, in_len, out, p.n, batch,
+                       (const uint64_t*)t.t0.p, (const uint64_t*)t.t1.p, t.bits, p.fa);
+  else
+    hipLaunchKernelGGL(coset_scale_kernel<Mod32>, grid, dim3(256), 0, s, in, in_len, out, p.n, batch,
+                       (const uint64_t*)t.t0.p, (const uint64_t*)t.t1.p, t.bits, p.fa);
+  PBF_HIP(hipGetLastError());
+  return 0;
+}
+
+int run_plan_coset(const NttPlan& p, uint64_t shift, const uint64_t* d_in, size_t in_len, uint64_t* d_out,
+                   size_t batch, DevBuf& s0, DevBuf& s1, hipStream_t stream, ForkSet* fork) {
+  if (batch == 0) return 0;
+  // n = 1 has the one factor shift^0; shift 1 on whole polynomials is the plain transform
+  if (p.n == 1 || (shift == 1 && in_len == p.n)) return run_plan_impl(p, d_in, d_out, batch, s0, s1, stream, 0, fork);
+  const CosetTabs* t;
+  int rc = coset_tabs(p, shift, p.inverse ? p.n : in_len, &t);
+  if (rc) return rc;
+  if (p.gl) {
+    const GlCoset cs{t, in_len};
+    return run_plan_impl(p, d_in, d_out, batch, s0, s1, stream, 0, fork, &cs);
+  }
+  if (p.inverse) {
+    if ((rc = run_plan_impl(p, d_in, d_out, batch, s0, s1, stream, 0, fork))) return rc;
+    return launch_coset_scale(p, *t, d_out, p.n, d_out, batch, stream);
+  }
+  if ((rc = launch_coset_scale(p, *t, d_in, in_len, d_out, batch, stream))) return rc;
+  return run_plan_impl(p, d_out, d_out, batch, s0, s1, stream, 0, fork);
 }
 
 // ---------------------------------------------------------------- pointwise

@@ -623,6 +623,27 @@ __global__ void k_powers29(uint64_t* out, uint64_t count, ScalePow29 sp) {
   }
 }
 
+// The coset scaling for the public Fr coset transforms (ntt256.hip pbf_ntt_fr256_coset*):
+// out[b*out_pitch + i] = in[b*len + i] * base^i, i < len, for `batch` polynomials (base in
+// Montgomery form, elements 4 x u64; in may equal out when out_pitch == len). The prover's own
+// calls (Prover::scale) do not come through here.
+int fr256_scale_pow(bool l29, const uint64_t* in, uint64_t len, uint64_t* out, uint64_t out_pitch, uint64_t batch,
+                    const U256& base, hipStream_t s) {
+  const ScalePow sp = scale_pow_tab(fr_one_m(), base, 0, 1);
+  const ScalePow29 sp29 = to29(sp);
+  const dim3 grid(blocks_for((len + PV_CHUNK - 1) / PV_CHUNK));
+  for (uint64_t b = 0; b < batch; ++b) {
+    if (l29)
+      hipLaunchKernelGGL(k_scale_pow29, grid, dim3(256), 0, s, in + 4 * len * b, (uint64_t)0, (uint64_t)1, len,
+                         out + 4 * out_pitch * b, len, sp29);
+    else
+      hipLaunchKernelGGL(k_scale_pow, grid, dim3(256), 0, s, in + 4 * len * b, (uint64_t)0, (uint64_t)1, len,
+                         out + 4 * out_pitch * b, len, sp);
+  }
+  PBF_HIP(hipGetLastError());
+  return 0;
+}
+
 static void launch_quotient(const QuotArgs& qa, uint64_t* out, bool l29, hipStream_t s) {
   const char* qc = ab_env("PBF_QUOT_CHUNK");
   const uint32_t qch = qc && atoi(qc) > 0 ? (uint32_t)atoi(qc) : 32;

@@ -107,6 +107,11 @@ SIGNATURES = [
                                                        _sz, ctypes.c_int, _p64, _p64, _vp]),
     ("pbf_multi_backend", ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int)]),
     ("pbf_msm_g1_bn254_fixed_range_dev", ctypes.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _p64, _vp]),
+    ("pbf_ntt_u64_coset", ctypes.c_int, [_vp, _u64, _u64, _u64, _p64, _sz, _p64, _sz, ctypes.c_int]),
+    ("pbf_ntt_u64_coset_batch_dev", ctypes.c_int, [_vp, _u64, _u64, _u64, _vp, _sz, _vp, _sz, _sz, ctypes.c_int,
+                                                   _vp]),
+    ("pbf_ntt_fr256_coset", ctypes.c_int, [_vp, _p64, _p64, _p64, _sz, _p64, _sz, ctypes.c_int]),
+    ("pbf_ntt_fr256_coset_batch_dev", ctypes.c_int, [_vp, _p64, _p64, _vp, _sz, _vp, _sz, _sz, ctypes.c_int, _vp]),
 ]
 
 _lib = None
@@ -202,6 +207,22 @@ class Context:
         _check(self.lib.pbf_ntt_u64_batch_dev(self.h, modulus, omega, _vp(d_in), _vp(d_out), n, batch,
                                               int(inverse), _vp(stream) if stream else None))
 
+    # the same transforms on the coset shift * <omega> (include/pbf.h "coset NTT"): forward is the
+    # low-degree extension of len(values) <= n coefficients to n evaluations
+    def ntt_coset(self, modulus: int, omega: int, shift: int, values, n: int | None = None,
+                  inverse: bool = False) -> np.ndarray:
+        a = _as_u64(values)
+        n = a.size if n is None else int(n)
+        out = np.empty(n, dtype=np.uint64)
+        _check(self.lib.pbf_ntt_u64_coset(self.h, modulus, omega, shift, _ptr(a), a.size, _ptr(out), n,
+                                          int(inverse)))
+        return out
+
+    def ntt_coset_batch_dev(self, modulus: int, omega: int, shift: int, d_in: int, in_len: int, d_out: int, n: int,
+                            batch: int, inverse: bool = False, stream: int = 0) -> None:
+        _check(self.lib.pbf_ntt_u64_coset_batch_dev(self.h, modulus, omega, shift, _vp(d_in), in_len, _vp(d_out), n,
+                                                    batch, int(inverse), _vp(stream) if stream else None))
+
     # fft.rs:109-132
     def mul_ntt(self, modulus: int, omega: int, a, b) -> np.ndarray:
         a = _as_u64(a)
@@ -295,6 +316,20 @@ class Context:
         w = ints_to_limbs([omega])
         _check(self.lib.pbf_ntt_fr256_batch_dev(self.h, _ptr(w), _vp(d_in), _vp(d_out), n, batch, int(inverse),
                                                 _vp(stream) if stream else None))
+
+    def ntt_fr_coset(self, omega: int, shift: int, values, n: int | None = None, inverse: bool = False) -> list:
+        a = ints_to_limbs(values)
+        n = len(values) if n is None else int(n)
+        out = np.empty(4 * n, dtype=np.uint64)
+        _check(self.lib.pbf_ntt_fr256_coset(self.h, _ptr(ints_to_limbs([omega])), _ptr(ints_to_limbs([shift])),
+                                            _ptr(a), len(values), _ptr(out), n, int(inverse)))
+        return limbs_to_ints(out)
+
+    def ntt_fr_coset_batch_dev(self, omega: int, shift: int, d_in: int, in_len: int, d_out: int, n: int, batch: int,
+                               inverse: bool = False, stream: int = 0) -> None:
+        _check(self.lib.pbf_ntt_fr256_coset_batch_dev(self.h, _ptr(ints_to_limbs([omega])),
+                                                      _ptr(ints_to_limbs([shift])), _vp(d_in), in_len, _vp(d_out), n,
+                                                      batch, int(inverse), _vp(stream) if stream else None))
 
     def mul_ntt_fr_dev(self, omega: int, d_a: int, d_b: int, d_out: int, n: int, batch: int, stream: int = 0):
         w = ints_to_limbs([omega])
@@ -670,6 +705,14 @@ class CooleyTurkey:
 
     def fft_inv(self, freq) -> np.ndarray:
         return self.ctx.ntt(self.modulus, self.domain.omega, freq, inverse=True)
+
+    def coset_fft(self, values, shift: int, n: int | None = None) -> np.ndarray:
+        """Evaluations of the polynomial `values` on shift * <omega_n> (n: the domain size, default
+        len(values); a larger power of two needs the matching `domain`): a low-degree extension."""
+        return self.ctx.ntt_coset(self.modulus, self.domain.omega, shift, values, n=n)
+
+    def coset_fft_inv(self, freq, shift: int) -> np.ndarray:
+        return self.ctx.ntt_coset(self.modulus, self.domain.omega, shift, freq, inverse=True)
 
 
 def mul_ntt(fft: CooleyTurkey, a_vals, b_vals) -> np.ndarray:
