@@ -86,8 +86,13 @@ struct GlPassArgs {
 
 // x * 2^(K mod 192) (mod p), K a compile-time exponent; 2^96 = -1. Exponents in
 // (160, 192) are divisions by 2^(192-K) (no sign); a remaining sign costs one subtraction.
+// 2^(K mod 192) = (-1)^gl_pow2_neg(K) * (what gl_pow2_abs<K> multiplies by)
+__host__ __device__ constexpr bool gl_pow2_neg(int k) {
+  const int raw = ((k % 192) + 192) % 192;
+  return raw > 64 && raw <= 160;  // (64, 96): -2^-(96-raw); [96, 160]: -2^(raw-96)
+}
 template <int K>
-__device__ __forceinline__ uint64_t gl_pow2(uint64_t x) {
+__device__ __forceinline__ uint64_t gl_pow2_abs(uint64_t x) {
   constexpr int RAW = ((K % 192) + 192) % 192;
   if constexpr (RAW == 0) {
     return x;
@@ -95,13 +100,18 @@ __device__ __forceinline__ uint64_t gl_pow2(uint64_t x) {
     return gl_div_pow2<192 - RAW>(x);
   } else {
     using T = ShiftKind<RAW>;
-    const uint64_t y = apply_shift<Goldilocks, T>(x);
-    if constexpr (T::NEG) {
-      const FieldArgs f{};
-      return Goldilocks::sub(0, y, f);
-    } else {
-      return y;
-    }
+    static_assert(T::NEG == gl_pow2_neg(K), "sign of 2^K");
+    return apply_shift<Goldilocks, T>(x);
+  }
+}
+template <int K>
+__device__ __forceinline__ uint64_t gl_pow2(uint64_t x) {
+  const uint64_t y = gl_pow2_abs<K>(x);
+  if constexpr (gl_pow2_neg(K)) {
+    const FieldArgs f{};
+    return Goldilocks::sub(0, y, f);
+  } else {
+    return y;
   }
 }
 
@@ -112,6 +122,35 @@ __device__ __forceinline__ void gl_stage_b_twiddle(uint64_t* v) {
     v[S2] = gl_pow2<(E64 * S2 * Q1) % 192>(v[S2]);
     gl_stage_b_twiddle<E64, Q1, S2 + 1>(v);
   }
+}
+// The same twiddle without its signs: v[s2] *= |2^(E64*s2*Q1)|, the negative powers (about half:
+// 4 VALU each as 0 - y) left to the 16-point DFT that follows, which takes their mask
+// gl_stage_b_negmask and folds every one of them into its butterflies (dft_reg_signed).
+template <int E64, int Q1, int S2 = 1>
+__device__ __forceinline__ void gl_stage_b_twiddle_abs(uint64_t* v) {
+  if constexpr (S2 < 16) {
+    v[S2] = gl_pow2_abs<(E64 * S2 * Q1) % 192>(v[S2]);
+    gl_stage_b_twiddle_abs<E64, Q1, S2 + 1>(v);
+  }
+}
+__host__ __device__ constexpr unsigned gl_stage_b_negmask(int e64, int q1) {
+  unsigned m = 0;
+  for (int s2 = 1; s2 < 16; ++s2) m |= gl_pow2_neg((e64 * s2 * q1) % 192) ? 1u << s2 : 0u;
+  return m;
+}
+// Levels of stage B's 16-point DFT that run per q1 (inside the wave-uniform switch) to absorb
+// the twiddle's signs: after two levels 0 / 1 / 1 (E64 = 39; 153: 2 / 2 / 1) of the 8 / 7 / 7
+// (9 / 8 / 8) signs of q1 = 1 / 2 / 3 are left and are negated there; the last two levels are
+// common code after the switch. (All four levels per q1 leave no sign at all but repeat the
+// whole DFT four times, +14 KB of code per kernel, for the same measured VALU count and a
+// step time 0.5 % higher; one level leaves 2 / 4 / 4: DESIGN.md §3.1 round 7.)
+constexpr int GL_B_LEVELS = 2;
+// stage B of one q1: twiddle and the first GL_B_LEVELS levels of the 16-point DFT over s2
+template <int E64, int Q1>
+__device__ __forceinline__ void gl_stage_b_head(uint64_t* v) {
+  const FieldArgs f{};
+  gl_stage_b_twiddle_abs<E64, Q1>(v);
+  dft_reg_signed<Goldilocks, 4, sub_root_exp(E64, 4), gl_stage_b_negmask(E64, Q1), GL_B_LEVELS>(v, f);
 }
 
 // v[bitrev4(e)] *= w_64^(e*Q) = 2^(E64*e*Q): a twiddle on the bit-reversed outputs of a
@@ -204,12 +243,19 @@ constexpr int GL_STORES = 16;  // global stores per thread per tile (NSUB_C * C)
 // RG (regrouped 2^24 plan, ntt_gl_rg2_kernel below): 1 = its first pass, 3 = its last pass.
 // CS (coset transforms): 1 = a first pass that scales its loads by shift^i and reads no zero
 // padding, 2 = a last pass that scales its stores by shift^-k n^-1 (GlPassArgs cs_*).
-template <int LOGR, int E64, bool FIRST, int TILE, int RG = 0, int CS = 0>
+// SP (the second pass of a plain forward two-pass plan, run_gl_group): the pass compiled with
+// only what such a plan executes: no pass-twiddle code (the first pass applied it: post_tw),
+// no scaled table and no split store. 1 = log_ns from the arguments, 2 = log_ns = LOGR (both
+// passes of one radix: the index arithmetic of the stores folds to constants). 0 = the generic
+// kernel of every other pass and plan. (The first pass with post_tw unconditional measured
+// no faster and 5.6 VALU per element more, DESIGN.md §3.1 round 7: it stays generic.)
+template <int LOGR, int E64, bool FIRST, int TILE, int RG = 0, int CS = 0, int SP = 0>
 __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint32_t tile, uint32_t tiles, int t) {
   using Sh = GlShape<LOGR, TILE>;
   constexpr int C = Sh::C, LOGC = Sh::LOGC, W = Sh::W, NT = Sh::NT, YP = Sh::YP;
   (void)YP;
   static_assert(Sh::NSUB_C * C == GL_STORES, "stores per thread");
+  static_assert(SP == 0 || (!FIRST && RG == 0 && CS == 0 && SP <= 2), "SP: second pass of a plain two-pass plan");
   static_assert(RG == 0 || (LOGR == 8 && TILE == 4096 && FIRST == (RG == 1)), "RG shape");
   static_assert(CS == 0 || (FIRST == (CS == 1) && (RG == 0 || RG == 2 * CS - 1)), "CS 1: first pass, CS 2: last pass");
   const FieldArgs f{};
@@ -267,7 +313,7 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
     t3[0] = a.tws_a[((uint64_t)r2 << 18) + X];
     t3[1] = a.tws_b[X];
   }
-  if constexpr (!FIRST && RG != 3) if (!a.skip_pass_tw) {
+  if constexpr (!FIRST && RG != 3 && SP == 0) if (!a.skip_pass_tw) {
     const uint64_t kmask = (1ull << a.log_ns) - 1;
     // in groups of 8 elements (loads of a group issue back to back; bounded live registers)
 #pragma unroll
@@ -327,15 +373,18 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
         v[s2] = G::mul(v[s2], p, f);
         if (s2 < 15) p = G::mul(p, d, f);
       }
+      dft_reg<G, 4, sub_root_exp(E64, 4)>(v, nullptr, f);
     } else {
+      // the twiddle's signs are folded into the DFT's first levels, whose butterflies then
+      // differ by q1
       switch (__builtin_amdgcn_readfirstlane(q1)) {
-        case 1: gl_stage_b_twiddle<E64, 1>(v); break;
-        case 2: gl_stage_b_twiddle<E64, 2>(v); break;
-        case 3: gl_stage_b_twiddle<E64, 3>(v); break;
-        default: break;
+        case 1: gl_stage_b_head<E64, 1>(v); break;
+        case 2: gl_stage_b_head<E64, 2>(v); break;
+        case 3: gl_stage_b_head<E64, 3>(v); break;
+        default: gl_stage_b_head<E64, 0>(v); break;
       }
+      dft_reg_tail<G, 4, sub_root_exp(E64, 4), GL_B_LEVELS>(v, f);
     }
-    dft_reg<G, 4, sub_root_exp(E64, 4)>(v, nullptr, f);
 #endif
     __syncthreads();
     const int r2 = rw / W, w = rw % W;
@@ -391,7 +440,8 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
     }
   } else {
     uint64_t tw[Sh::NSUB_C * C];
-    const int r2lo = a.scaled ? 0 : 1;  // scaled table carries n^-1: every element multiplies
+    const bool scaled = SP == 0 && a.scaled;
+    const int r2lo = scaled ? 0 : 1;  // scaled table carries n^-1: every element multiplies
 #pragma unroll
     for (int u = 0; u < Sh::NSUB_C; ++u) {
       int k1, w;
@@ -399,7 +449,7 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
 #pragma unroll
       for (int r2 = 0; r2 < C; ++r2) tw[u * C + r2] = (r2 >= r2lo) ? a.tc[r2 * 64 + k1] : 1;
     }
-    if (a.scaled) {
+    if (scaled) {
 #pragma unroll
       for (int m = 0; m < Sh::NSUB_C * C; ++m) PBF_GL_MATH(x[m] = G::mul(x[m], tw[m], f));
     } else {
@@ -442,32 +492,33 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
           o[base + k1 + 64 * k2] = x[u * C + bitrev_c(k2, LOGC)];
     }
   } else {
-    const uint64_t ns_mask = (1ull << a.log_ns) - 1;
+    const uint32_t lns = SP == 2 ? (uint32_t)LOGR : a.log_ns;
+    const uint64_t ns_mask = (1ull << lns) - 1;
     uint64_t* out = a.out + (uint64_t)poly * a.out_pitch;
-    const uint32_t sl = a.out_split_log;
+    const uint32_t sl = SP != 0 ? 0u : a.out_split_log;
 #pragma unroll
     for (int u = 0; u < Sh::NSUB_C; ++u) {
       int k1, w;
       c_map(u, &k1, &w);
       const uint64_t j = j0 + w;
-      const uint64_t base = ((j >> a.log_ns) << (a.log_ns + LOGR)) + (j & ns_mask);
+      const uint64_t base = ((j >> lns) << (lns + LOGR)) + (j & ns_mask);
       if (sl == 0) {
         if constexpr (CS == 2) {
           uint64_t tw[C];
 #pragma unroll
-          for (int k2 = 0; k2 < C; ++k2) tw[k2] = gl_cs_factor(a, base + ((uint64_t)(k1 + 64 * k2) << a.log_ns));
+          for (int k2 = 0; k2 < C; ++k2) tw[k2] = gl_cs_factor(a, base + ((uint64_t)(k1 + 64 * k2) << lns));
 #pragma unroll
           for (int k2 = 0; k2 < C; ++k2) x[u * C + bitrev_c(k2, LOGC)] = G::mul(x[u * C + bitrev_c(k2, LOGC)], tw[k2], f);
         }
 #pragma unroll
         for (int k2 = 0; k2 < C; ++k2)
           if (!PBF_GL_NOMEM_ON || x[u * C + bitrev_c(k2, LOGC)] == 0x123456789ull)
-            out[base + ((uint64_t)(k1 + 64 * k2) << a.log_ns)] = x[u * C + bitrev_c(k2, LOGC)];
+            out[base + ((uint64_t)(k1 + 64 * k2) << lns)] = x[u * C + bitrev_c(k2, LOGC)];
       } else {
         const uint64_t smask = (1ull << sl) - 1;
 #pragma unroll
         for (int k2 = 0; k2 < C; ++k2) {
-          const uint64_t kk = base + ((uint64_t)(k1 + 64 * k2) << a.log_ns);
+          const uint64_t kk = base + ((uint64_t)(k1 + 64 * k2) << lns);
           a.out[((((kk >> sl) * a.batch) + poly) << sl) + (kk & smask)] = x[u * C + bitrev_c(k2, LOGC)];
         }
       }
@@ -484,7 +535,7 @@ __device__ __forceinline__ void gl_shape_checks() {
 }
 
 // One tile per workgroup.
-template <int LOGR, int E64, bool FIRST, int TILE, int RG = 0, int CS = 0>
+template <int LOGR, int E64, bool FIRST, int TILE, int RG = 0, int CS = 0, int SP = 0>
 // waves per SIMD the VGPR budget allows: 5 where the LDS allows five workgroups and the
 // kernel fits 96 VGPRs without spilling (first passes and the regrouped plan's), else 4
 __global__ void __launch_bounds__(TILE / 16)
@@ -493,7 +544,7 @@ ntt_gl_pass_kernel(GlPassArgs a) {
   gl_shape_checks<LOGR, TILE>();
   __shared__ __attribute__((aligned(16))) uint64_t lds[GlShape<LOGR, TILE>::LDS];
   const uint32_t tiles = a.blocks_per_poly * a.batch;
-  gl_tile<LOGR, E64, FIRST, TILE, RG, CS>(a, lds, blockIdx.x, tiles, threadIdx.x);
+  gl_tile<LOGR, E64, FIRST, TILE, RG, CS, SP>(a, lds, blockIdx.x, tiles, threadIdx.x);
 }
 
 // ---- regrouped 2^24 plan (DESIGN.md §3.1 "Regrouped twiddles") --------------------------

@@ -139,6 +139,75 @@ __device__ __forceinline__ void dft_reg(uint64_t* v, const uint64_t* wq, const F
   dif_levels<F, LOGQ, E, (1 << LOGQ) / 2>(v, wq, f);
 }
 
+// dft_reg (E >= 0) over inputs of which some hold the negated value: bit i of M set means
+// v[i] = -(input i). A sign costs nothing inside a butterfly: with x, y the stored values,
+//   signs equal:   sum = +-(x + y), the sign stays on the sum; difference = +-(x - y), folded
+//                  into the operand order of the subtraction together with the twiddle's (NEG);
+//   signs differ:  sum = x - y or y - x (no sign left); difference = +-(x + y), the sign
+//                  (times the twiddle's) stays on that output for the next level.
+// What is left after the last level is negated there (none for the stage-B twiddles of
+// ntt_gl.hpp). Every operation returns the canonical value of the same field element as the
+// unsigned form, so the results are bit-identical.
+__host__ __device__ constexpr bool dif_tw_neg(int e, int logq, int h, int a) {
+  const int raw = (e * a * ((1 << logq) / (2 * h))) % 192;  // as TwShift / ShiftKind::NEG
+  const bool neg0 = raw >= 96;
+  return (neg0 ? raw - 96 : raw) > 64 ? !neg0 : neg0;
+}
+// sign mask after the level of half-size H
+template <int LOGQ, int E, int H>
+__host__ __device__ constexpr unsigned dif_level_mask(unsigned m) {
+  unsigned r = 0;
+  for (int i = 0; i < (1 << LOGQ) / 2; ++i) {
+    const int a = i % H, lo = (i / H) * 2 * H + a, hi = lo + H;
+    const bool nx = (m >> lo) & 1, ny = (m >> hi) & 1;
+    if (nx == ny) r |= nx ? 1u << lo : 0u;
+    else if (nx != dif_tw_neg(E, LOGQ, H, a)) r |= 1u << hi;
+  }
+  return r;
+}
+template <class F, int LOGQ, int E, int H, unsigned M, int I = 0>
+__device__ __forceinline__ void dif_level_s(uint64_t* v, const FieldArgs& f) {
+  if constexpr (I < (1 << LOGQ) / 2) {
+    constexpr int A = I % H, lo = (I / H) * 2 * H + A, hi = lo + H;
+    constexpr bool nx = (M >> lo) & 1, ny = (M >> hi) & 1;
+    using T = TwShift<E, LOGQ, H, A>;  // A = 0: 2^0, no shift and no sign
+    static_assert(T::NEG == dif_tw_neg(E, LOGQ, H, A), "twiddle sign");
+    const uint64_t x = v[lo], y = v[hi];
+    uint64_t d;
+    if constexpr (nx == ny) {
+      v[lo] = F::add(x, y, f);
+      d = (nx != T::NEG) ? F::sub(y, x, f) : F::sub(x, y, f);
+    } else {
+      v[lo] = nx ? F::sub(y, x, f) : F::sub(x, y, f);
+      d = F::add(x, y, f);
+    }
+    v[hi] = apply_shift<F, T>(d);
+    dif_level_s<F, LOGQ, E, H, M, I + 1>(v, f);
+  }
+}
+template <class F, int LOGQ, int E, int H, int HSTOP, unsigned M>
+__device__ __forceinline__ void dif_levels_s(uint64_t* v, const FieldArgs& f) {
+  if constexpr (H > HSTOP) {
+    dif_level_s<F, LOGQ, E, H, M>(v, f);
+    dif_levels_s<F, LOGQ, E, H / 2, HSTOP, dif_level_mask<LOGQ, E, H>(M)>(v, f);
+  } else {
+#pragma unroll
+    for (int i = 0; i < (1 << LOGQ); ++i)
+      if ((M >> i) & 1) v[i] = F::sub(0, v[i], f);
+  }
+}
+// The first LEVELS levels of dft_reg over signed inputs (mask M); the caller finishes with
+// dft_reg_tail, which is the same code for every M.
+template <class F, int LOGQ, int E, unsigned M, int LEVELS = LOGQ>
+__device__ __forceinline__ void dft_reg_signed(uint64_t* v, const FieldArgs& f) {
+  static_assert(E >= 0 && LOGQ <= 5 && LEVELS >= 1 && LEVELS <= LOGQ, "shift twiddles; one mask bit per element");
+  dif_levels_s<F, LOGQ, E, (1 << LOGQ) / 2, (((1 << LOGQ) / 2) >> LEVELS), M>(v, f);
+}
+template <class F, int LOGQ, int E, int LEVELS>
+__device__ __forceinline__ void dft_reg_tail(uint64_t* v, const FieldArgs& f) {
+  dif_levels<F, LOGQ, E, (((1 << LOGQ) / 2) >> LEVELS)>(v, nullptr, f);
+}
+
 // Exponent of w_q = 2^E given w_64 = 2^E64 (E64 < 0: table twiddles).
 __host__ __device__ constexpr int sub_root_exp(int e64, int logq) {
   return e64 < 0 ? -1 : (e64 * (64 >> logq)) % 192;

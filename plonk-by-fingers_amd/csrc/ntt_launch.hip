@@ -397,6 +397,13 @@ static GlPassFn gl_fn_cs(int logr, int cs) {
   }
 }
 
+// plain forward two-pass plans whose second pass is radix 2^10 (the 2^20 default "10,10"): that
+// pass compiled with only what such a plan executes (ntt_gl.hpp SP). same_radix: the first pass
+// is radix 2^10 too, so the second pass's log_ns is the constant 10.
+static GlPassFn gl_fn_sp10(bool same_radix) {
+  return same_radix ? ntt_gl_pass_kernel<10, 39, false, 8192, 0, 0, 2> : ntt_gl_pass_kernel<10, 39, false, 8192, 0, 0, 1>;
+}
+
 // the regrouped 2^24 plan's three pass kernels
 template <int E>
 static GlPassFn gl_fn_rg(int pass) {
@@ -437,21 +444,39 @@ ForkSet::~ForkSet() {
   if (fork) (void)hipEventDestroy(fork);
 }
 
+// The group schedule of a batched Goldilocks plan: G polynomials per group (0: the whole batch
+// is one group) over ns streams.
+// default schedule (measured best at 2^20 x 32): groups of 4 polynomials
+// alternating over the caller's stream and a second one once the batch has at least 8, so the
+// passes of two groups run concurrently and their load / compute / store phases interleave
+// (options ntt.group = polynomials per group, ntt.streams = streams; 0 or >= batch: one group)
+static void gl_schedule(const NttPlan& p, size_t batch, uint32_t split_log, const ForkSet* fork, size_t* G, int* ns) {
+  const long long go = p.opts.num("ntt.group", -1);
+  *G = go >= 0 ? (size_t)go : (batch >= 8 ? 4 : batch);
+  if (split_log != 0 || *G >= batch) *G = 0;
+  *ns = (int)p.opts.num("ntt.streams", 2);
+  *ns = *ns < 1 ? 1 : (*ns > GL_MAX_STREAMS ? GL_MAX_STREAMS : *ns);
+  if (!fork || *G == 0) *ns = 1;
+}
+
+// Polynomials of intermediate scratch that schedule needs. The groups of one stream run one
+// after another, so they share one slot of G polynomials (run_gl_passes): the intermediates of
+// a 2^20 x 32 batch take 64 MiB, not 256 MiB, and stay within the 256 MiB Infinity Cache.
+static size_t gl_scratch_polys(const NttPlan& p, size_t batch, uint32_t split_log, const ForkSet* fork) {
+  size_t G;
+  int ns;
+  gl_schedule(p, batch, split_log, fork, &G, &ns);
+  return (G == 0 || G * ns > batch) ? batch : G * ns;
+}
+
 static int run_gl_passes(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out, size_t batch, DevBuf& s0,
                          DevBuf& s1, hipStream_t stream, uint32_t split_log, ForkSet* fork, const GlCoset* cs) {
-  // default schedule (measured best at 2^20 x 32): groups of 4 polynomials
-  // alternating over the caller's stream and a second one once the batch has at least 8, so the
-  // passes of two groups run concurrently and their load / compute / store phases interleave
-  // (options ntt.group = polynomials per group, ntt.streams = streams; 0 or >= batch: one group)
-  const long long go = p.opts.num("ntt.group", -1);
-  const size_t G = go >= 0 ? (size_t)go : (batch >= 8 ? 4 : batch);
-  if (split_log != 0 || G == 0 || G >= batch)
-    return run_gl_group(p, d_in, d_out, batch, s0, s1, stream, split_log, 0, cs);
+  size_t G;
+  int ns;
+  gl_schedule(p, batch, split_log, fork, &G, &ns);
+  if (G == 0) return run_gl_group(p, d_in, d_out, batch, s0, s1, stream, split_log, 0, cs);
   // a forward coset transform reads compact polynomials of in_len coefficients
   const size_t in_pitch = (cs && !p.inverse) ? cs->in_len : p.n;
-  int ns = (int)p.opts.num("ntt.streams", 2);
-  ns = ns < 1 ? 1 : (ns > GL_MAX_STREAMS ? GL_MAX_STREAMS : ns);
-  if (!fork) ns = 1;
   hipStream_t sts[GL_MAX_STREAMS];
   sts[0] = stream;
   // Fork and join by events: a stream waiting on an event waits in the command processor
@@ -469,8 +494,9 @@ static int run_gl_passes(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out
   int gi = 0;
   for (size_t g0 = 0; g0 < batch; g0 += G, ++gi) {
     const size_t b = batch - g0 < G ? batch - g0 : G;
+    // scratch ring: one slot of G polynomials per stream (a stream's groups are serialised)
     const int rc = run_gl_group(p, d_in + g0 * in_pitch, d_out + g0 * p.n, b, s0, s1, sts[gi % ns], 0,
-                                ns > 1 ? g0 * p.n : 0, cs);
+                                (size_t)(gi % ns) * G * p.n, cs);
     if (rc) return rc;
   }
   for (int i = 1; i < ns; ++i) {
@@ -546,6 +572,9 @@ static int run_gl_group(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out,
     const int csv = !cs ? 0 : (!p.inverse && i == 0) ? 1 : (p.inverse && i == P - 1) ? 2 : 0;
     if (csv && rg) fn = p.e64 == 39 ? gl_fn_rg_cs<39>(csv) : gl_fn_rg_cs<153>(csv);
     else if (csv) fn = p.e64 == 39 ? gl_fn_cs<39>(lr, csv) : gl_fn_cs<153>(lr, csv);
+    // two-pass plans whose first pass applies the second pass's twiddle (post_tw below)
+    const bool two_pass_tw = P == 2 && split_log == 0 && p.twpass[1]->p;
+    if (two_pass_tw && i == 1 && !cs && !p.inverse && p.e64 == 39 && lr == 10) fn = gl_fn_sp10(p.logr[0] == 10);
     if (!fn) return fail(1, "no Goldilocks pass kernel for this radix");
     const uint64_t W = (uint64_t)tile >> lr;
     if ((p.n >> lr) % W) return fail(1, "transform too small for the pass tile");
@@ -579,7 +608,7 @@ static int run_gl_group(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out,
     // 0.354-0.357 ms against 0.368-0.371 linear, profiles/r04/ntt_orders_sweep.log)
     a.post_tw = nullptr;
     a.skip_pass_tw = 0;
-    if (P == 2 && split_log == 0 && p.twpass[1]->p) {
+    if (two_pass_tw) {
       if (i == 0) a.post_tw = (const uint64_t*)p.twpass[1]->p;
       else a.skip_pass_tw = 1;
     }
@@ -637,7 +666,7 @@ static int run_plan_impl(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out
     return 0;
   }
   const size_t P = p.logr.size();
-  const size_t bytes = batch * p.n * 8;
+  const size_t bytes = (p.gl ? gl_scratch_polys(p, batch, split_log, fork) : batch) * p.n * 8;
   int rc = s0.ensure(bytes);
   if (!rc && P > 2) rc = s1.ensure(bytes);
   if (rc) return rc;
