@@ -311,6 +311,43 @@ int pbf_plonk_verify_bn254_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, cons
                                const uint64_t* proof_f, const uint64_t* chal, const uint64_t* u, const uint64_t* k1k2,
                                int mode, int* ok, void* stream);
 
+/* Batched Plonk::verify: `count` proofs of ONE circuit and SRS, one 2-pair pairing check.
+ * Per proof i the single verifier checks e(E1_i, [s]G2) == e(E2_i, G2) with
+ * E1_i = W_z,i + u_i W_zw,i and E2_i the 18-term combination of the proof's points, the
+ * circuit's 8 preprocessed commitments and G. The batch checks the random linear combination
+ *     e(sum_i rho_i E1_i, [s]G2) * e(-sum_i rho_i E2_i, G2) == 1
+ * as one MSM over 9 count + 9 points, one over 2 count points and one pairing check, whatever
+ * `count` is. Arrays are proof-major, host pointers in both forms (as the single verifier
+ * takes its proof): proof_pts count x 9 x 8, proof_f count x 7 x 4, chal count x 5 x 4
+ * (alpha beta gamma z v per proof), u count x 4, rho count x 4. The circuit, SRS, g2, k1k2,
+ * mode, the stream contract, the verification-key cache and option verifier.vk are those of
+ * pbf_plonk_verify_bn254 / _dev.
+ * Randomness: the library reads none. Soundness rests on the caller choosing the weights rho
+ * unpredictably and AFTER seeing the proofs (e.g. by hashing all of them); with predictable or
+ * equal weights the errors of two bad proofs can cancel and the batch passes. rho_0 = 1 is
+ * fine; 128-bit weights are enough.
+ * Result: a proof is rejected outright when one of its 9 points is not canonical or not on the
+ * curve ((0,0) is accepted), one of its 7 fields is >= r, or Z_H(z_i) = 0 -- the single
+ * verifier's ok = 0 cases. *ok = 1 iff no proof is rejected and the combined check passes.
+ * ok_each (count ints, or NULL): rejected proofs get 0; if the combined check over the others
+ * passes they all get 1; if not, the index range is halved recursively down to single proofs
+ * (a one-proof range is the single verifier's equation times rho_i != 0), reusing the
+ * per-proof scalars on the device: each range costs its two MSMs and one pairing check. With
+ * NULL no localisation runs.
+ * Errors (PBF_EINVAL, before anything is enqueued): count = 0 or > 2^20, a rho_i that is zero
+ * or >= r, and every error of the single verifier (NULL arguments, bad n, short SRS). chal
+ * and u are taken as the single verifier takes them: any 256-bit value, reduced mod r.      */
+int pbf_plonk_verify_bn254_batch(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies,
+                                 const uint64_t* srs, size_t srs_m, const uint64_t* g2, size_t count,
+                                 const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* chal,
+                                 const uint64_t* u, const uint64_t* rho, const uint64_t* k1k2, int mode, int* ok,
+                                 int* ok_each);
+int pbf_plonk_verify_bn254_batch_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
+                                     const uint64_t* d_srs, size_t srs_m, const uint64_t* g2, size_t count,
+                                     const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* chal,
+                                     const uint64_t* u, const uint64_t* rho, const uint64_t* k1k2, int mode, int* ok,
+                                     int* ok_each, void* stream);
+
 /* Config 5 across G GPUs ("NTT sharded across 8xMI355X"): one process (or thread) per GPU
  * calls pbf_plonk_prove_bn254_sharded_dev with the same inputs (circuit, SRS, challenges,
  * blinders) and its rank. The library computes nothing collective itself: it calls back

@@ -2271,6 +2271,10 @@ void h_neg_g1(const uint64_t* p, uint64_t* out) {
 
 }  // namespace
 
+static int verify_with_vk(pbf_ctx* ctx, size_t n, const U256& omega, const uint64_t (*pre)[8], const uint64_t* d_srs,
+                          const uint64_t* g2, const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* chal,
+                          const uint64_t* u_in, const uint64_t* k1k2, int mode, int* ok, hipStream_t s);
+
 // Plonk::verify (src/plonk.rs:468-650). srs: >= n affine G1 points (g1s, device), g2: [g2_1, g2_s]
 // (2 x 16 u64, host); proof as pbf_plonk_prove_bn254 returns it; u the verifier's random
 // scalar (rand[0], plonk.rs:519). mode 0 keeps step 7's t_z (plonk.rs:575-581, no alpha on
@@ -2288,20 +2292,33 @@ extern "C" int pbf_plonk_verify_bn254_dev(pbf_ctx* ctx, size_t n, const uint64_t
   uint32_t log_n = 0;
   while ((1ull << log_n) < n) ++log_n;
   hipStream_t s = (hipStream_t)stream;
-  const uint64_t E = 32;
   int rc;
   // Step 1-2: proof points on the curve, proof fields canonical (plonk.rs:523-547)
   for (int i = 0; i < 9; ++i)
     if (!h_on_curve(proof_pts + 8 * i)) return 0;
   for (int i = 0; i < 7; ++i)
     if (Fr::geq_p(u256_from_u64(proof_f + 4 * i))) return 0;
+  const U256 omega = hroot(log_n);
+  uint64_t pre[8][8];
+  if ((rc = verifier_vk(ctx, n, omega, d_q, d_copies, d_srs, srs_m, k1k2, s, pre))) return rc;
+  return verify_with_vk(ctx, n, omega, pre, d_srs, g2, proof_pts, proof_f, chal, u_in, k1k2, mode, ok, s);
+}
+
+// Plonk::verify's preprocessing, shared by the single and the batched verifier
+// (verify_batch.hip): pre = the commitments of q_m q_l q_r q_o q_c s_sigma_1..3; omega =
+// fr_root_of_unity(log2 n).
+U256 pbf::fr_root_of_unity(uint32_t log_n) { return hroot(log_n); }
+
+int pbf::verifier_vk(pbf_ctx* ctx, size_t n, const U256& omega, const uint64_t* d_q, const uint64_t* d_copies,
+                     const uint64_t* d_srs, size_t srs_m, const uint64_t* k1k2, hipStream_t s, uint64_t pre[8][8]) {
+  const uint64_t E = 32;
+  int rc;
   // preprocessing (plonk.rs:507-517): commitments of q_m q_l q_r q_o q_c, s_sigma_1..3 -- a
   // verification key: kept in the context for this circuit and SRS (q, copies and the SRS
   // compared with device copies of the ones it was built from on every call;
   // PBF_VERIFIER_NO_VK=1 recomputes them, as the reference does)
-  const U256 omega = hroot(log_n), one = fr_one_m();
+  const U256 one = fr_one_m();
   const U256 k1 = hm(k1k2), k2 = hm(k1k2 + 4);
-  uint64_t pre[8][8];
   std::vector<uint64_t> vk_key;
   const bool vk_on = ctx->options.num("verifier.vk", 1) != 0;
   if (vk_on) {
@@ -2315,7 +2332,7 @@ extern "C" int pbf_plonk_verify_bn254_dev(pbf_ctx* ctx, size_t n, const uint64_t
     for (int i = 0; i < 8; ++i) vk_key.push_back(k1k2[i]);
   }
   if (vk_on && ctx->vk_key == vk_key && ctx->vk_pts.size() == 64) {
-    memcpy(pre, ctx->vk_pts.data(), sizeof(pre));
+    memcpy(pre, ctx->vk_pts.data(), 64 * sizeof(uint64_t));
   } else {
   DevBuf &hp = ctx->buf("vf.hpow"), &sg = ctx->buf("vf.sigma"), &cf = ctx->buf("vf.coef"), &fl = ctx->buf("vf.flag");
   if ((rc = hp.ensure(n * E)) || (rc = sg.ensure(3 * n * E)) || (rc = cf.ensure(8 * n * E)) || (rc = fl.ensure(64)))
@@ -2360,7 +2377,16 @@ extern "C" int pbf_plonk_verify_bn254_dev(pbf_ctx* ctx, size_t n, const uint64_t
     ctx->vk_pts.assign(&pre[0][0], &pre[0][0] + 64);
   }
   }
+  return 0;
+}
 
+// Plonk::verify steps 4-12 for one proof whose points and fields passed steps 1-2
+static int verify_with_vk(pbf_ctx* ctx, size_t n, const U256& omega, const uint64_t (*pre)[8], const uint64_t* d_srs,
+                          const uint64_t* g2, const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* chal,
+                          const uint64_t* u_in, const uint64_t* k1k2, int mode, int* ok, hipStream_t s) {
+  const U256 one = fr_one_m();
+  const U256 k1 = hm(k1k2), k2 = hm(k1k2 + 4);
+  int rc;
   const U256 alpha = hm(chal), beta = hm(chal + 4), gamma = hm(chal + 8), zc = hm(chal + 12), v = hm(chal + 16);
   const U256 u = hm(u_in);
   const U256 a_z = hm(proof_f), b_z = hm(proof_f + 4), c_z = hm(proof_f + 8), s1_z = hm(proof_f + 12),

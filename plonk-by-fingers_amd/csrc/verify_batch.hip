@@ -1,0 +1,427 @@
+// Batched Plonk::verify over BN254 on gfx950: `count` proofs of one circuit, one 2-pair
+// pairing check (include/pbf.h pbf_plonk_verify_bn254_batch*).
+//
+// The single verifier (prover.hip "Plonk::verify") checks, per proof i,
+//     e(E1_i, [s]G2) == e(E2_i, G2),   E1_i = W_z,i + u_i W_zw,i,   E2_i = sum_j scal_ij base_ij
+// with 18 bases: the proof's 9 points, the circuit's 8 preprocessed commitments and G. The
+// pairing is bilinear, so for caller-chosen weights rho_i
+//     e(sum_i rho_i E1_i, [s]G2) == e(sum_i rho_i E2_i, G2)
+// holds when every proof's equation does, and fails with overwhelming probability over
+// unpredictable rho when one does not. The 9 shared bases collect sum_i rho_i scal_ij, so the
+// batch is one MSM over 9 count + 9 points, one over 2 count points and one pairing check.
+//
+// Work split:
+//   k_vb_curve    one lane per proof POINT: canonical coordinates, y^2 = x^3 + 3 in Fq; ORs
+//                 into the proof's flag; gathers W_z, W_zw into the compact E1 point array
+//   k_vb_scalars  one lane per PROOF (blocks of one wave): fields canonical, Z_H(z) != 0, then
+//                 the single verifier's Fr formulas (steps 4-10) scaled by rho_i; a flagged
+//                 proof's scalars are written as zero, so its points ride through the MSM inert
+//   k_vb_colsum*  the 9 shared-base scalars of an index range [lo, hi): LDS tree per block,
+//                 second step across blocks (field addition is exact: any order, same limbs)
+// Every scalar is the canonical value the host formulas give. Localisation (ok_each) halves the
+// index range, recomputing only the column sums, the two MSMs and the pairing per range.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+#include "../../include/pbf.h"
+#include "msm.hpp"
+
+using namespace pbf;
+
+namespace {
+
+constexpr uint32_t VB_PART = 64;  // column-sum partial blocks per column (one wave in step 2)
+// The E1 MSM runs over W_z, W_zw gathered compactly (2 count points). The A/B build (make
+// vbfull) runs it over all 9 count proof points in place with 7 zero scalars per proof instead.
+#ifdef PBF_VB_E1_FULL
+constexpr uint32_t E1_N = 9, E1_AT = 7;
+#else
+constexpr uint32_t E1_N = 2, E1_AT = 0;
+#endif
+
+struct VbParams {
+  U256 k1, k2, omega, n_inv;  // Montgomery
+  uint32_t log_n, count;
+  int mode;
+};
+
+__device__ __forceinline__ U256 ldm(const uint64_t* p) { return Fr::to_mont(u256_from_u64(p)); }
+__device__ __forceinline__ void stm(uint64_t* p, const U256& m) { u256_to_u64(Fr::from_mont(m), p); }
+// one copy of the product's code per kernel: the scalar kernel is ~120 products of straight line
+__device__ __noinline__ U256 fmul(U256 a, U256 b) { return Fr::mul(a, b); }
+
+// a^(r-2): Fermat inverse (a != 0)
+__device__ U256 vb_inv(const U256& a, const U256& one) {
+  U256 r = one;
+#pragma unroll 1
+  for (int i = 255; i >= 0; --i) {
+    r = fmul(r, r);
+    const uint32_t e = Bn254FrParams::P[i / 32] - (i < 32 ? 2u : 0u);
+    if ((e >> (i % 32)) & 1) r = fmul(r, a);
+  }
+  return r;
+}
+
+__device__ __forceinline__ void st_zero(uint64_t* p) { p[0] = p[1] = p[2] = p[3] = 0; }
+
+// flag bits: 1 a point not canonical / off the curve, 2 a field >= r, 4 Z_H(z) = 0
+__global__ void __launch_bounds__(256) k_vb_curve(const uint64_t* pts, uint32_t npts, int* flag, uint64_t* e1pts) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= npts) return;
+  const uint32_t i = t / 9, j = t % 9;
+  const uint64_t* p = pts + 8 * (uint64_t)t;
+  uint64_t l[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) l[k] = p[k];
+  if (j >= 7) {
+    uint64_t* o = e1pts + 8 * ((uint64_t)2 * i + (j - 7));
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = l[k];
+  }
+  uint64_t any = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) any |= l[k];
+  if (any == 0) return;  // the identity (0, 0) is accepted (G1P::in_curve)
+  const U256 x = u256_from_u64(l), y = u256_from_u64(l + 4);
+  bool bad = Fq::geq_p(x) || Fq::geq_p(y);
+  if (!bad) {
+    const U256 xm = Fq::to_mont(x), ym = Fq::to_mont(y);
+    U256 three = u256_zero();
+    three.w[0] = 3;
+    const U256 rhs = Fq::add(Fq::mul(Fq::mul(xm, xm), xm), Fq::to_mont(three));
+    bad = !Fq::eq(Fq::mul(ym, ym), rhs);
+  }
+  if (bad) atomicOr(flag + i, 1);
+}
+
+// prover.hip steps 4-10 for proof i = one lane, every output times rho_i:
+//   sc[9 i + j]      j < 9: a b c z t_lo t_mid t_hi w_z w_zw
+//   e1s[E1_N i + E1_AT + 0, 1]  rho, rho u
+//   contrib[j][i]    j < 9: q_m q_l q_r q_o q_c s1 s2 (-d3 on s3) (-E on G)
+__global__ void __launch_bounds__(64) k_vb_scalars(const uint64_t* __restrict__ pf, const uint64_t* __restrict__ chal,
+                                                   const uint64_t* __restrict__ u_in, const uint64_t* __restrict__ rho_in,
+                                                   VbParams P, int* flag, uint64_t* sc, uint64_t* e1s,
+                                                   uint64_t* contrib) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= P.count) return;
+  const uint64_t* f = pf + 28 * (uint64_t)i;
+  const uint64_t* ch = chal + 20 * (uint64_t)i;
+  int bad = flag[i];
+  for (int k = 0; k < 7; ++k)
+    if (Fr::geq_p(u256_from_u64(f + 4 * k))) bad |= 2;
+  const U256 one = Fr::to_mont(Fr::one_plain());
+  const U256 zc = ldm(ch + 12);
+  // Step 4: Z_H(z) = z^n - 1
+  U256 zn = zc;
+#pragma unroll 1
+  for (uint32_t k = 0; k < P.log_n; ++k) zn = fmul(zn, zn);
+  const U256 z_h_z = Fr::sub(zn, one);
+  if (Fr::is_zero(z_h_z)) bad |= 4;
+  if (bad) {
+    flag[i] = bad;
+    for (int j = 0; j < 9; ++j) st_zero(sc + 4 * ((uint64_t)9 * i + j));
+    for (uint32_t j = 0; j < E1_N; ++j) st_zero(e1s + 4 * ((uint64_t)E1_N * i + j));
+    for (int j = 0; j < 9; ++j) st_zero(contrib + 4 * ((uint64_t)j * P.count + i));
+    return;
+  }
+  const U256 alpha = ldm(ch), beta = ldm(ch + 4), gamma = ldm(ch + 8), v = ldm(ch + 16);
+  const U256 u = ldm(u_in + 4 * (uint64_t)i), rho = ldm(rho_in + 4 * (uint64_t)i);
+  const U256 a_z = ldm(f), b_z = ldm(f + 4), c_z = ldm(f + 8), s1_z = ldm(f + 12), s2_z = ldm(f + 16),
+             r_z = ldm(f + 20), zw_z = ldm(f + 24);
+  // Step 5: L_1(z) = (z^n - 1) / (n (z - 1)); z = 1 has Z_H = 0 and never gets here, so one
+  // inversion of Z_H(z) (z - 1) serves both quotients
+  const U256 zm1 = Fr::sub(zc, one);
+  const U256 tinv = vb_inv(fmul(z_h_z, zm1), one);
+  const U256 inv_zh = fmul(tinv, zm1);
+  const U256 l1 = fmul(fmul(z_h_z, fmul(tinv, z_h_z)), P.n_inv);
+  // Step 7: t_z
+  const U256 alpha2 = fmul(alpha, alpha);
+  const U256 l1a2 = fmul(l1, alpha2);
+  const U256 pa = Fr::add(Fr::add(a_z, fmul(beta, s1_z)), gamma);
+  const U256 pb = Fr::add(Fr::add(b_z, fmul(beta, s2_z)), gamma);
+  const U256 pab = fmul(pa, pb);
+  U256 perm = fmul(pab, fmul(Fr::add(c_z, gamma), zw_z));
+  if (P.mode == 1) perm = fmul(perm, alpha);
+  const U256 t_z = fmul(Fr::sub(Fr::sub(r_z, perm), l1a2), inv_zh);
+  // Steps 8-10
+  U256 vp[7];
+  vp[0] = one;
+  for (int k = 1; k < 7; ++k) vp[k] = fmul(vp[k - 1], v);
+  const U256 bz = fmul(beta, zc);
+  const U256 d2 = Fr::add(
+      Fr::add(fmul(fmul(fmul(fmul(Fr::add(Fr::add(a_z, bz), gamma), Fr::add(Fr::add(b_z, fmul(bz, P.k1)), gamma)),
+                             Fr::add(Fr::add(c_z, fmul(bz, P.k2)), gamma)),
+                        alpha),
+                   v),
+              fmul(l1a2, v)),
+      u);
+  const U256 d3 = fmul(fmul(fmul(fmul(pab, alpha), v), beta), zw_z);
+  U256 ecoef = Fr::add(t_z, fmul(v, r_z));
+  ecoef = Fr::add(ecoef, fmul(vp[2], a_z));
+  ecoef = Fr::add(ecoef, fmul(vp[3], b_z));
+  ecoef = Fr::add(ecoef, fmul(vp[4], c_z));
+  ecoef = Fr::add(ecoef, fmul(vp[5], s1_z));
+  ecoef = Fr::add(ecoef, fmul(vp[6], s2_z));
+  ecoef = Fr::add(ecoef, fmul(u, zw_z));
+  const U256 zn2 = fmul(zn, fmul(zc, zc));  // z^(n+2)
+  const U256 zero = u256_zero();
+  uint64_t* o = sc + 4 * (uint64_t)9 * i;
+  stm(o, fmul(rho, vp[2]));                       // a_s
+  stm(o + 4, fmul(rho, vp[3]));                   // b_s
+  stm(o + 8, fmul(rho, vp[4]));                   // c_s
+  stm(o + 12, fmul(rho, d2));                     // z_s
+  stm(o + 16, rho);                               // t_lo
+  stm(o + 20, fmul(rho, zn2));                    // t_mid
+  stm(o + 24, fmul(rho, fmul(zn2, zn2)));         // t_hi: z^(2n+4)
+  stm(o + 28, fmul(rho, zc));                     // w_z * z
+  const U256 ru = fmul(rho, u);
+  stm(o + 32, fmul(ru, fmul(zc, P.omega)));       // w_zw * u z w
+  for (uint32_t j = 0; j < E1_AT; ++j) st_zero(e1s + 4 * ((uint64_t)E1_N * i + j));
+  stm(e1s + 4 * ((uint64_t)E1_N * i + E1_AT), rho);
+  stm(e1s + 4 * ((uint64_t)E1_N * i + E1_AT + 1), ru);
+  const U256 rv = fmul(rho, v);
+  const uint64_t cs = (uint64_t)4 * P.count;
+  uint64_t* c = contrib + 4 * (uint64_t)i;
+  stm(c, fmul(rv, fmul(a_z, b_z)));               // q_m
+  stm(c + cs, fmul(rv, a_z));                     // q_l
+  stm(c + 2 * cs, fmul(rv, b_z));                 // q_r
+  stm(c + 3 * cs, fmul(rv, c_z));                 // q_o
+  stm(c + 4 * cs, rv);                            // q_c
+  stm(c + 5 * cs, fmul(rho, vp[5]));              // s1
+  stm(c + 6 * cs, fmul(rho, vp[6]));              // s2
+  stm(c + 7 * cs, Fr::sub(zero, fmul(rho, d3)));  // - s3 d3
+  stm(c + 8 * cs, Fr::sub(zero, fmul(rho, ecoef)));  // - E
+}
+
+// canonical residues add like any others: no Montgomery conversion in the sums
+__device__ __forceinline__ U256 block_sum(U256 acc, U256* sh) {
+  const uint32_t t = threadIdx.x;
+  sh[t] = acc;
+  __syncthreads();
+  for (uint32_t w = blockDim.x / 2; w; w >>= 1) {
+    if (t < w) sh[t] = Fr::add(sh[t], sh[t + w]);
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+// part[j][b] = sum of contrib[j][i] over this block's share of [lo, hi); grid (nb <= VB_PART, 9)
+__global__ void __launch_bounds__(256) k_vb_colsum(const uint64_t* contrib, uint32_t count, uint32_t lo, uint32_t hi,
+                                                   uint64_t* part) {
+  __shared__ U256 sh[256];
+  const uint32_t j = blockIdx.y;
+  U256 acc = u256_zero();
+  for (uint64_t i = (uint64_t)lo + blockIdx.x * 256u + threadIdx.x; i < hi; i += (uint64_t)gridDim.x * 256u)
+    acc = Fr::add(acc, u256_from_u64(contrib + 4 * ((uint64_t)j * count + i)));
+  acc = block_sum(acc, sh);
+  if (threadIdx.x == 0) u256_to_u64(acc, part + 4 * ((uint64_t)j * VB_PART + blockIdx.x));
+}
+
+// out[j] = sum_b part[j][b]; grid 9, one wave
+__global__ void __launch_bounds__(64) k_vb_colsum2(const uint64_t* part, uint32_t nb, uint64_t* out) {
+  __shared__ U256 sh[VB_PART];
+  const uint32_t j = blockIdx.x;
+  U256 acc = u256_zero();
+  if (threadIdx.x < nb) acc = u256_from_u64(part + 4 * ((uint64_t)j * VB_PART + threadIdx.x));
+  acc = block_sum(acc, sh);
+  if (threadIdx.x == 0) u256_to_u64(acc, out + 4 * j);
+}
+
+// (x, q - y), the identity unchanged
+void neg_g1(const uint64_t* p, uint64_t* out) {
+  for (int i = 0; i < 8; ++i) out[i] = p[i];
+  const U256 y = u256_from_u64(p + 4);
+  if (Fq::is_zero(y)) return;
+  U256 d;
+  uint64_t borrow = 0;
+  for (int i = 0; i < 8; ++i) {
+    const uint64_t t = (uint64_t)Bn254FqParams::P[i] - y.w[i] - borrow;
+    d.w[i] = (uint32_t)t;
+    borrow = (t >> 63) & 1;
+  }
+  u256_to_u64(d, out + 4);
+}
+
+struct Batch {
+  pbf_ctx* ctx;
+  hipStream_t s;
+  const uint64_t* g2;
+  size_t count;
+  uint64_t *pts, *sc, *e1p, *e1s, *contrib, *part;
+  const int* hflag;  // host copy of the per-proof flags (valid after the first MSM's sync)
+  int* each;
+
+  // the combined equation over proofs [lo, hi): column sums, two MSMs, one pairing check
+  int check(size_t lo, size_t hi, int* ok) {
+    const size_t len = hi - lo;
+    int rc;
+    uint64_t *P = pts, *S = sc;
+    if (len != count) {  // a sub-range: its points and scalars, then the shared bases, contiguous
+      DevBuf &wp = ctx->buf("vb.wpts"), &ws = ctx->buf("vb.wsc");
+      if ((rc = wp.ensure((9 * len + 9) * 64)) || (rc = ws.ensure((9 * len + 9) * 32))) return rc;
+      P = (uint64_t*)wp.p;
+      S = (uint64_t*)ws.p;
+      PBF_HIP(hipMemcpyAsync(P, pts + 72 * lo, 9 * len * 64, hipMemcpyDeviceToDevice, s));
+      PBF_HIP(hipMemcpyAsync(P + 72 * len, pts + 72 * count, 9 * 64, hipMemcpyDeviceToDevice, s));
+      PBF_HIP(hipMemcpyAsync(S, sc + 36 * lo, 9 * len * 32, hipMemcpyDeviceToDevice, s));
+    }
+    const uint32_t nb = (uint32_t)std::min<size_t>((len + 255) / 256, VB_PART);
+    hipLaunchKernelGGL(k_vb_colsum, dim3(nb, 9), dim3(256), 0, s, (const uint64_t*)contrib, (uint32_t)count,
+                       (uint32_t)lo, (uint32_t)hi, part);
+    hipLaunchKernelGGL(k_vb_colsum2, dim3(9), dim3(64), 0, s, (const uint64_t*)part, nb, S + 36 * len);
+    PBF_HIP(hipGetLastError());
+    uint64_t e1[8], e2[8];
+    if ((rc = pbf_msm_g1_bn254_dev(ctx, P, S, 9 * len + 9, e2, s))) return rc;
+    if ((rc = pbf_msm_g1_bn254_dev(ctx, E1_N == 9 ? pts + 72 * lo : e1p + 16 * lo, e1s + 4 * E1_N * lo, E1_N * len, e1,
+                                   s)))
+      return rc;
+    // e(sum rho E1, [s]G2) e(-sum rho E2, G2) == 1
+    uint64_t g1s[16], g2s[32];
+    memcpy(g1s, e1, 64);
+    neg_g1(e2, g1s + 8);
+    memcpy(g2s, g2 + 16, 128);  // [s]G2
+    memcpy(g2s + 16, g2, 128);  // G2
+    return pairing_check_on_stream(ctx, g1s, g2s, 2, ok, s);
+  }
+
+  // ok_each over [lo, hi) by halving. failed: the range's equation is already known to fail
+  // (its parent failed and its sibling passed: the sums are linear), so it is not run again.
+  int localise(size_t lo, size_t hi, bool failed, bool* passed) {
+    size_t live = 0;
+    for (size_t i = lo; i < hi; ++i) live += hflag[i] == 0;
+    *passed = true;
+    if (!live) return 0;  // only rejected proofs: every scalar is zero
+    int rc, ok = 0;
+    if (!failed && (rc = check(lo, hi, &ok))) return rc;
+    if (ok) {
+      for (size_t i = lo; i < hi; ++i) each[i] = hflag[i] == 0;
+      return 0;
+    }
+    *passed = false;
+    if (hi - lo == 1) return 0;  // each[lo] stays 0
+    const size_t mid = lo + (hi - lo) / 2;
+    bool left = false, right = false;
+    if ((rc = localise(lo, mid, false, &left))) return rc;
+    return localise(mid, hi, left, &right);
+  }
+};
+
+bool fr_canonical(const uint64_t* p) { return !Fr::geq_p(u256_from_u64(p)); }
+
+// every argument error, before anything is enqueued. chal and u are taken as the single
+// verifier takes them (prover.hip hm()): any 256-bit value, reduced mod r.
+int vb_validate(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies, const uint64_t* srs, size_t srs_m,
+                const uint64_t* g2, size_t count, const uint64_t* proof_pts, const uint64_t* proof_f,
+                const uint64_t* chal, const uint64_t* u, const uint64_t* rho, const uint64_t* k1k2, int* ok) {
+  if (!ctx || !q || !copies || !srs || !g2 || !proof_pts || !proof_f || !chal || !u || !rho || !k1k2 || !ok)
+    return fail(PBF_EINVAL, "null argument");
+  *ok = 0;
+  if (n < 8 || (n & (n - 1))) return fail(PBF_EINVAL, "n must be a power of two >= 8");
+  if (srs_m < n) return fail(PBF_EINVAL, "SRS too short");
+  if (count == 0 || count > ((size_t)1 << 20)) return fail(PBF_EINVAL, "count must be in 1 .. 2^20");
+  for (size_t i = 0; i < count; ++i) {
+    const uint64_t* r = rho + 4 * i;
+    if (!fr_canonical(r) || !(r[0] | r[1] | r[2] | r[3])) return fail(PBF_EINVAL, "rho must be canonical and nonzero");
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int pbf_plonk_verify_bn254_batch_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
+                                                const uint64_t* d_srs, size_t srs_m, const uint64_t* g2, size_t count,
+                                                const uint64_t* proof_pts, const uint64_t* proof_f,
+                                                const uint64_t* chal, const uint64_t* u, const uint64_t* rho,
+                                                const uint64_t* k1k2, int mode, int* ok, int* ok_each, void* stream) {
+  int rc;
+  if ((rc = vb_validate(ctx, n, d_q, d_copies, d_srs, srs_m, g2, count, proof_pts, proof_f, chal, u, rho, k1k2, ok)))
+    return rc;
+  PBF_HIP(hipSetDevice(ctx->device));
+  uint32_t log_n = 0;
+  while ((1ull << log_n) < n) ++log_n;
+  hipStream_t s = (hipStream_t)stream;
+  const U256 omega = fr_root_of_unity(log_n);
+  uint64_t pre[8][8];
+  if ((rc = verifier_vk(ctx, n, omega, d_q, d_copies, d_srs, srs_m, k1k2, s, pre))) return rc;
+
+  const size_t c = count;
+  DevBuf &bp = ctx->buf("vb.pts"), &bs = ctx->buf("vb.sc"), &bf = ctx->buf("vb.f"), &bc = ctx->buf("vb.chal"),
+         &bu = ctx->buf("vb.u"), &br = ctx->buf("vb.rho"), &bfl = ctx->buf("vb.flag"), &bq = ctx->buf("vb.e1p"),
+         &bt = ctx->buf("vb.e1s"), &bk = ctx->buf("vb.contrib"), &bpart = ctx->buf("vb.part");
+  if ((rc = bp.ensure((9 * c + 9) * 64)) || (rc = bs.ensure((9 * c + 9) * 32)) || (rc = bf.ensure(7 * c * 32)) ||
+      (rc = bc.ensure(5 * c * 32)) || (rc = bu.ensure(c * 32)) || (rc = br.ensure(c * 32)) ||
+      (rc = bfl.ensure(c * sizeof(int))) || (rc = bq.ensure(2 * c * 64)) || (rc = bt.ensure(E1_N * c * 32)) ||
+      (rc = bk.ensure(9 * c * 32)) || (rc = bpart.ensure(9 * VB_PART * 32)))
+    return rc;
+  uint64_t* pts = (uint64_t*)bp.p;
+  // bases: the proofs' points in place, then q_m q_l q_r q_o q_c s1 s2 s3 and G
+  PBF_HIP(hipMemcpyAsync(pts, proof_pts, 9 * c * 64, hipMemcpyHostToDevice, s));
+  PBF_HIP(hipMemcpyAsync(pts + 72 * c, &pre[0][0], 8 * 64, hipMemcpyHostToDevice, s));
+  PBF_HIP(hipMemcpyAsync(pts + 72 * c + 64, d_srs, 64, hipMemcpyDeviceToDevice, s));
+  PBF_HIP(hipMemcpyAsync(bf.p, proof_f, 7 * c * 32, hipMemcpyHostToDevice, s));
+  PBF_HIP(hipMemcpyAsync(bc.p, chal, 5 * c * 32, hipMemcpyHostToDevice, s));
+  PBF_HIP(hipMemcpyAsync(bu.p, u, c * 32, hipMemcpyHostToDevice, s));
+  PBF_HIP(hipMemcpyAsync(br.p, rho, c * 32, hipMemcpyHostToDevice, s));
+  PBF_HIP(hipMemsetAsync(bfl.p, 0, c * sizeof(int), s));
+  VbParams P;
+  P.k1 = Fr::to_mont(u256_from_u64(k1k2));
+  P.k2 = Fr::to_mont(u256_from_u64(k1k2 + 4));
+  P.omega = omega;
+  {  // n^-1 = (2^-1)^log_n, 2^-1 = (r + 1) / 2
+    U256 h;
+    for (int i = 0; i < 8; ++i) h.w[i] = Bn254FrParams::P[i];
+    h.w[0] += 1;  // r is odd and its low limb is not all ones: no carry
+    for (int i = 0; i < 8; ++i) h.w[i] = (h.w[i] >> 1) | (i < 7 ? (h.w[i + 1] << 31) : 0);
+    const U256 half = Fr::to_mont(h);
+    U256 ni = Fr::to_mont(Fr::one_plain());
+    for (uint32_t k = 0; k < log_n; ++k) ni = Fr::mul(ni, half);
+    P.n_inv = ni;
+  }
+  P.log_n = log_n;
+  P.count = (uint32_t)c;
+  P.mode = mode;
+  const uint32_t npts = (uint32_t)(9 * c);
+  hipLaunchKernelGGL(k_vb_curve, dim3((npts + 255) / 256), dim3(256), 0, s, (const uint64_t*)pts, npts, (int*)bfl.p,
+                     (uint64_t*)bq.p);
+  hipLaunchKernelGGL(k_vb_scalars, dim3((uint32_t)((c + 63) / 64)), dim3(64), 0, s, (const uint64_t*)bf.p,
+                     (const uint64_t*)bc.p, (const uint64_t*)bu.p, (const uint64_t*)br.p, P, (int*)bfl.p,
+                     (uint64_t*)bs.p, (uint64_t*)bt.p, (uint64_t*)bk.p);
+  PBF_HIP(hipGetLastError());
+  std::vector<int> hflag(c);
+  PBF_HIP(hipMemcpyAsync(hflag.data(), bfl.p, c * sizeof(int), hipMemcpyDeviceToHost, s));
+
+  Batch B{ctx, s, g2, c, pts, (uint64_t*)bs.p, (uint64_t*)bq.p, (uint64_t*)bt.p, (uint64_t*)bk.p, (uint64_t*)bpart.p,
+          hflag.data(), ok_each};
+  int all = 0;
+  if ((rc = B.check(0, c, &all))) return rc;  // synchronises s: hflag is complete
+  bool rejected = false;
+  for (size_t i = 0; i < c; ++i) rejected = rejected || hflag[i] != 0;
+  *ok = all && !rejected;
+  if (!ok_each) return 0;
+  for (size_t i = 0; i < c; ++i) ok_each[i] = all && hflag[i] == 0;
+  if (all || c == 1) return 0;
+  const size_t mid = c / 2;
+  bool left = false, right = false;
+  if ((rc = B.localise(0, mid, false, &left))) return rc;
+  return B.localise(mid, c, left, &right);
+}
+
+extern "C" int pbf_plonk_verify_bn254_batch(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies,
+                                            const uint64_t* srs, size_t srs_m, const uint64_t* g2, size_t count,
+                                            const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* chal,
+                                            const uint64_t* u, const uint64_t* rho, const uint64_t* k1k2, int mode,
+                                            int* ok, int* ok_each) {
+  int rc;
+  if ((rc = vb_validate(ctx, n, q, copies, srs, srs_m, g2, count, proof_pts, proof_f, chal, u, rho, k1k2, ok)))
+    return rc;
+  PBF_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->host_stream();
+  DevBuf &dq = ctx->buf("vf.q"), &dc = ctx->buf("vf.copies"), &dsrs = ctx->buf("vf.srs");
+  if ((rc = dq.ensure(5 * n * 32)) || (rc = dc.ensure(3 * n * 16)) || (rc = dsrs.ensure(srs_m * 64))) return rc;
+  PBF_HIP(hipMemcpyAsync(dq.p, q, 5 * n * 32, hipMemcpyHostToDevice, s));
+  PBF_HIP(hipMemcpyAsync(dc.p, copies, 3 * n * 16, hipMemcpyHostToDevice, s));
+  PBF_HIP(hipMemcpyAsync(dsrs.p, srs, srs_m * 64, hipMemcpyHostToDevice, s));
+  return pbf_plonk_verify_bn254_batch_dev(ctx, n, (const uint64_t*)dq.p, (const uint64_t*)dc.p,
+                                          (const uint64_t*)dsrs.p, srs_m, g2, count, proof_pts, proof_f, chal, u, rho,
+                                          k1k2, mode, ok, ok_each, s);
+}

@@ -81,6 +81,12 @@ SIGNATURES = [
                                               ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     ("pbf_plonk_verify_bn254_dev", ctypes.c_int, [_vp, _sz, _vp, _vp, _vp, _sz, _p64, _p64, _p64, _p64, _p64, _p64,
                                                   ctypes.c_int, ctypes.POINTER(ctypes.c_int), _vp]),
+    ("pbf_plonk_verify_bn254_batch", ctypes.c_int, [_vp, _sz, _p64, _p64, _p64, _sz, _p64, _sz, _p64, _p64, _p64,
+                                                    _p64, _p64, _p64, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                                    ctypes.POINTER(ctypes.c_int)]),
+    ("pbf_plonk_verify_bn254_batch_dev", ctypes.c_int, [_vp, _sz, _vp, _vp, _vp, _sz, _p64, _sz, _p64, _p64, _p64,
+                                                        _p64, _p64, _p64, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                                        ctypes.POINTER(ctypes.c_int), _vp]),
     ("pbf_plonk_prove_bn254_sharded_dev", ctypes.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _p64, _p64, _p64, _vp, _sz,
                                                          ctypes.c_int, _p64, _p64, _vp]),
     ("pbf_plonk_synth_circuit_bn254_dev", ctypes.c_int, [_vp, _sz, _u64, _vp, _vp, _vp, _vp]),
@@ -438,6 +444,53 @@ class Context:
                                                    _ptr(ints_to_limbs(chal)), _ptr(ints_to_limbs([u])),
                                                    _ptr(ints_to_limbs(k1k2)), mode, ctypes.byref(ok), stream))
         return ok.value == 1
+
+    @staticmethod
+    def _batch_arrays(proofs, chals, us, rhos):
+        """Proof-major limb arrays of a batch: proofs a list of (pts, fields) as the provers return
+        them (points / ints, or limb arrays); chals a list of 5-tuples; us, rhos lists of ints."""
+        count = len(proofs)
+        if not (len(chals) == len(us) == len(rhos) == count):
+            raise ValueError("proofs, chals, us and rhos must have one entry per proof")
+        pa = np.zeros(72 * count, dtype=np.uint64)
+        fa = np.zeros(28 * count, dtype=np.uint64)
+        for i, (pts, fields) in enumerate(proofs):
+            pa[72 * i:72 * i + 72] = pts if isinstance(pts, np.ndarray) else _g1_limbs(pts)
+            fa[28 * i:28 * i + 28] = fields if isinstance(fields, np.ndarray) else ints_to_limbs(fields)
+        ca = ints_to_limbs([x for ch in chals for x in ch]) if count else np.zeros(0, dtype=np.uint64)
+        ua = ints_to_limbs(list(us)) if count else np.zeros(0, dtype=np.uint64)
+        ra = ints_to_limbs(list(rhos)) if count else np.zeros(0, dtype=np.uint64)
+        return count, pa, fa, ca, ua, ra
+
+    def plonk_verify_bn254_batch(self, q, copies, srs, g2s, proofs, chals, us, rhos, k1k2=(2, 3), mode=0,
+                                 each=False):
+        """pbf_plonk_verify_bn254_batch: many proofs of one circuit, one pairing check. rhos are the
+        batching weights: nonzero, < r, chosen unpredictably after seeing the proofs (soundness
+        rests on that; include/pbf.h). Returns ok, or (ok, [ok_i]) with each=True."""
+        n = len(q[0])
+        qa = ints_to_limbs([x for col in q for x in col])
+        ca = np.array([v for col in copies for (k, i) in col for v in (k, i)], dtype=np.uint64)
+        sa = _g1_limbs(srs)
+        count, pa, fa, cha, ua, ra = self._batch_arrays(proofs, chals, us, rhos)
+        ok = ctypes.c_int(-1)
+        oe = (ctypes.c_int * max(count, 1))() if each else None
+        _check(self.lib.pbf_plonk_verify_bn254_batch(self.h, n, _ptr(qa), _ptr(ca), _ptr(sa), len(srs),
+                                                     _ptr(_g2_limbs(g2s)), count, _ptr(pa), _ptr(fa), _ptr(cha),
+                                                     _ptr(ua), _ptr(ra), _ptr(ints_to_limbs(k1k2)), mode,
+                                                     ctypes.byref(ok), oe))
+        return (ok.value == 1, [bool(v) for v in oe[:count]]) if each else ok.value == 1
+
+    def plonk_verify_bn254_batch_dev(self, n, d_q, d_copies, d_srs, srs_m, g2s, proofs, chals, us, rhos,
+                                     k1k2=(2, 3), mode=0, each=False, stream: int = 0):
+        """The same with the circuit and SRS on the device (shaped like plonk_verify_bn254_dev)."""
+        count, pa, fa, cha, ua, ra = self._batch_arrays(proofs, chals, us, rhos)
+        ok = ctypes.c_int(-1)
+        oe = (ctypes.c_int * max(count, 1))() if each else None
+        _check(self.lib.pbf_plonk_verify_bn254_batch_dev(self.h, n, d_q, d_copies, d_srs, srs_m,
+                                                         _ptr(_g2_limbs(g2s)), count, _ptr(pa), _ptr(fa), _ptr(cha),
+                                                         _ptr(ua), _ptr(ra), _ptr(ints_to_limbs(k1k2)), mode,
+                                                         ctypes.byref(ok), oe, stream))
+        return (ok.value == 1, [bool(v) for v in oe[:count]]) if each else ok.value == 1
 
     def plonk_prove_bn254_sharded_dev(self, comm: "Comm", n, d_q, d_copies, d_abc, chal, rnd, d_srs, srs_m,
                                       k1k2=(2, 3), mode=0, stream: int = 0):
