@@ -152,6 +152,7 @@ constexpr int GL_MAX_STREAMS = 8;
 struct ForkSet {
   int device = 0;
   hipStream_t aux[GL_MAX_STREAMS] = {};  // aux[0] unused: slot 0 is the caller's stream
+  // device-to-device ordering only: created without timing and without a system-scope fence
   hipEvent_t fork = nullptr, join[GL_MAX_STREAMS] = {};
   int ensure(int streams);               // streams 1..streams-1 and the event pair exist
   ~ForkSet();

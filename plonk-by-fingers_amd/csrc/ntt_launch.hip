@@ -424,10 +424,14 @@ static int run_gl_group(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out,
 
 int ForkSet::ensure(int streams) {
   if (streams > GL_MAX_STREAMS) streams = GL_MAX_STREAMS;
-  if (streams > 1 && !fork) PBF_HIP(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
+  // The events order kernels of one device against each other, so they carry no system-scope
+  // fence: what the host sees is settled by the caller's own synchronisation or copy on their
+  // stream (the argument and the measurement)
+  const unsigned flags = hipEventDisableTiming | hipEventDisableSystemFence;
+  if (streams > 1 && !fork) PBF_HIP(hipEventCreateWithFlags(&fork, flags));
   for (int i = 1; i < streams; ++i) {
     if (!aux[i]) PBF_HIP(hipStreamCreateWithFlags(&aux[i], hipStreamNonBlocking));
-    if (!join[i]) PBF_HIP(hipEventCreateWithFlags(&join[i], hipEventDisableTiming));
+    if (!join[i]) PBF_HIP(hipEventCreateWithFlags(&join[i], flags));
   }
   return 0;
 }
