@@ -348,6 +348,57 @@ int pbf_plonk_verify_bn254_batch_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q
                                      const uint64_t* u, const uint64_t* rho, const uint64_t* k1k2, int mode, int* ok,
                                      int* ok_each, void* stream);
 
+/* ---- KZG commitments over BN254 (the scheme inside Plonk::prove / verify, on its own) ------
+ * Elements as above: Fr canonical 4 x u64, G1 affine 8 x u64 with (0,0) the identity, G2 16 x u64;
+ * srs = [G, sG, s^2 G, ...] as pbf_srs_create_bn254 writes it (G = (1, 2)), g2 = [G2, [s]G2].
+ * `batch` polynomials of `len` coefficients each, polynomial b starting at element b * pitch
+ * (pitch >= len). Results come back on the host, synchronised on the context's host stream
+ * (host forms) or the given stream (_dev forms: device srs and polynomials, everything else on the
+ * host), as pbf_msm_g1_bn254_fixed_dev returns its point; the stream contract, the side stream of
+ * the fixed-base MSM and its cached window table of the SRS (keyed by the points and srs_m) are
+ * that entry point's.
+ *
+ * pbf_poly_eval_fr256: Poly::eval (poly.rs:71-79) over Fr, the twin of pbf_poly_eval_u64:
+ *   ys[i] = sum_j coeffs[j] * xs[i]^j for n >= 1 coefficients and nx >= 1 points (repeats allowed);
+ *   coefficients and points are checked canonical.
+ * pbf_kzg_commit_bn254*: SRS::eval_at_s (plonk.rs:51-58), out_pts[b] = sum_j p_b[j] * srs[j]: one
+ *   fixed-base MSM per polynomial. Needs srs_m >= len.
+ * pbf_kzg_open_bn254*: the batched opening at one point (plonk.rs:429-446):
+ *     out_y[b] = p_b(z),     out_w = commit( (sum_b weights_b (p_b(x) - out_y[b])) / (x - z) ).
+ *   The weights are explicit (the prover's are 1, z^(n+2), z^(2n+4), v, v^2, ..., not pure powers).
+ *   The prover's own sequence: chunked Horner evaluations, the weighted sum of the polynomials,
+ *   one synthetic division by (x - z), then one fixed-base MSM over the quotient. Needs
+ *   srs_m >= len - 1; with len = 1 the quotient is empty and out_w is the identity.
+ *   z and the weights may be any canonical values, 0 included; z may be a root of a polynomial or
+ *   a point of any NTT domain: synthetic division has no failing case and none is added.
+ * pbf_kzg_verify_bn254: `count` openings (C_i, z_i, y_i, W_i), host pointers:
+ *     *ok = [ e(sum_i rho_i W_i, [s]G2) * e(-sum_i rho_i (C_i - y_i G + z_i W_i), G2) == 1 ]
+ *   as one MSM over count points, one over 2 count + 1 points and one pairing check, whatever
+ *   `count` is. count = 1, rho = 1 is the single check of plonk.rs:641-650. A batched opening
+ *   enters as one entry: C = sum_b weights_b C_b, y = sum_b weights_b y_b.
+ *   Randomness: the library reads none (the contract of pbf_plonk_verify_bn254_batch). Soundness
+ *   rests on the caller choosing the weights rho unpredictably and AFTER seeing the openings
+ *   (e.g. by hashing all of them); with predictable or equal weights the errors of two bad
+ *   entries can cancel (y_0 + d, y_1 - d at one z under rho = 1, 1) and the batch passes.
+ *   A point that is not canonical or not on the curve gives *ok = 0 outright ((0,0) is accepted);
+ *   there is no per-entry localisation.
+ * Errors (PBF_EINVAL, before anything is enqueued; never an abort): NULL pointers; len = 0,
+ * batch = 0 or batch > 2^16; count = 0 or count > 2^20; pitch < len; a short SRS; a host scalar
+ * (z, a weight, y, rho) >= r; rho_i = 0.                                                       */
+int pbf_poly_eval_fr256(pbf_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64_t* xs, size_t nx, uint64_t* ys);
+int pbf_kzg_commit_bn254(pbf_ctx* ctx, const uint64_t* srs, size_t srs_m, const uint64_t* polys, size_t len,
+                         size_t pitch, size_t batch, uint64_t* out_pts);
+int pbf_kzg_commit_bn254_dev(pbf_ctx* ctx, const uint64_t* d_srs, size_t srs_m, const uint64_t* d_polys, size_t len,
+                             size_t pitch, size_t batch, uint64_t* out_pts, void* stream);
+int pbf_kzg_open_bn254(pbf_ctx* ctx, const uint64_t* srs, size_t srs_m, const uint64_t* polys, size_t len,
+                       size_t pitch, size_t batch, const uint64_t* z, const uint64_t* weights, uint64_t* out_y,
+                       uint64_t* out_w);
+int pbf_kzg_open_bn254_dev(pbf_ctx* ctx, const uint64_t* d_srs, size_t srs_m, const uint64_t* d_polys, size_t len,
+                           size_t pitch, size_t batch, const uint64_t* z, const uint64_t* weights, uint64_t* out_y,
+                           uint64_t* out_w, void* stream);
+int pbf_kzg_verify_bn254(pbf_ctx* ctx, const uint64_t* g2, size_t count, const uint64_t* commits, const uint64_t* z,
+                         const uint64_t* y, const uint64_t* w, const uint64_t* rho, int* ok);
+
 /* Config 5 across G GPUs ("NTT sharded across 8xMI355X"): one process (or thread) per GPU
  * calls pbf_plonk_prove_bn254_sharded_dev with the same inputs (circuit, SRS, challenges,
  * blinders) and its rank. The library computes nothing collective itself: it calls back

@@ -30,6 +30,7 @@
 #include <vector>
 #include "../../include/pbf.h"
 #include "msm.hpp"
+#include "kzg.hpp"
 #include "fr29.hpp"
 
 // ntt256.hip: the coset transforms' batched forward NTT of zero-padded prefixes
@@ -681,16 +682,7 @@ static void launch_quotient(const QuotArgs& qa, uint64_t* out, bool l29, hipStre
 // consecutive k runs its recurrence from 0 (per thread, then a Hillis-Steele pass over the
 // threads with multipliers z^(HS_PER 2^j)) and leaves its total; (2) one block turns the
 // totals into each block's incoming s (multiplier z^HS_BLK); (3) s_k += z^(k - k_b + 1) s_in.
-constexpr int HS_T = 256, HS_PER = 16, HS_BLK = HS_T * HS_PER, HS_LOG_T = 8;
-// Conversion-free: the recurrence is linear with Montgomery-form multipliers (z, z^k), so
-// canonical coefficients give canonical s_k, totals and quotients throughout.
-struct HsArgs {
-  const uint64_t* p;
-  uint64_t L;
-  U256 y;                 // subtracted from p_0 (canonical)
-  U256 z;                 // Montgomery
-  U256 zs[HS_LOG_T];      // z^(HS_PER 2^j)
-};
+// (HS_T, HS_PER, HS_BLK, HS_LOG_T and HsArgs: kzg.hpp, shared with the KZG opening)
 // q[L-2-k] <- block-local s_k (k < L-1); the block-local remainder candidate in rem[block]
 // (v[] lives in scratch here (528 B per lane); compile-time indices keep it in 213 VGPRs at two
 // waves per SIMD, which measured 4 % slower: 1.74 against 1.68 ms for the two 2^24 divisions)
@@ -1044,6 +1036,58 @@ struct ProverBufs {
         partial(c->buf("pv.partial")) {}
 };
 
+// ---------------------------------------------------------------- kzg.hpp: the launchers shared
+// with the KZG entry points
+void hs_set_point(HsArgs& a, const U256& z) {
+  a.z = z;
+  for (int j = 0; j < HS_LOG_T; ++j) a.zs[j] = hpow64(z, (uint64_t)HS_PER << j);
+}
+int hs_div_run(pbf_ctx* ctx, const HsArgs& a, uint64_t* q, uint64_t* rem, hipStream_t s) {
+  const uint64_t nb = (a.L + HS_BLK - 1) / HS_BLK;
+  DevBuf& hb = ctx->buf("pv.hs");
+  int rc = hb.ensure(nb * 32);
+  if (rc) return rc;
+  uint64_t* totals = (uint64_t*)hb.p;
+  hipLaunchKernelGGL(k_hs1, dim3((uint32_t)nb), dim3(HS_T), 0, s, a, q, totals, rem);
+  const U256 zb = hpow64(a.z, HS_BLK);
+  hipLaunchKernelGGL(k_hs2, dim3(1), dim3(HS_T), 0, s, totals, nb, zb, hpow64(zb, (nb + HS_T - 1) / HS_T));
+  hipLaunchKernelGGL(k_hs3, dim3((uint32_t)nb), dim3(HS_T), 0, s, q, a.L, a, (const uint64_t*)totals, rem);
+  PBF_HIP(hipGetLastError());
+  return 0;
+}
+int fr_eval_run(const uint64_t* const* polys, const uint64_t* lens, const U256* xs, int np, DevBuf& partial,
+                uint64_t* d_evals, hipStream_t s) {
+  if (np < 1 || np > 12) return fail(PBF_EINVAL, "1 .. 12 polynomials per evaluation launch");
+  EvalArgs e;
+  uint64_t longest = 0;
+  for (int p = 0; p < np; ++p) {
+    e.poly[p] = polys[p];
+    e.len[p] = lens[p];
+    e.x[p] = xs[p];
+    e.off[p] = 0;
+    longest = std::max(longest, lens[p]);
+  }
+  e.chunks = (longest + (uint64_t)EV_T * EV_PER - 1) / ((uint64_t)EV_T * EV_PER);
+  int rc = launch_eval(e, np, partial, d_evals, s);
+  if (rc) return rc;
+  PBF_HIP(hipGetLastError());
+  return 0;
+}
+int fr_lincomb_run(const uint64_t* const* in, const U256* c, int k, uint64_t len, uint64_t* out, hipStream_t s) {
+  if (k < 1 || k > 10) return fail(PBF_EINVAL, "1 .. 10 inputs per linear combination");
+  LinComb L;
+  for (int i = 0; i < k; ++i) {
+    L.in[i] = in[i];
+    L.len[i] = len;
+    L.c[i] = c[i];
+  }
+  L.k = k;
+  L.c0 = u256_zero();
+  hipLaunchKernelGGL(k_lincomb, dim3(blocks_for(len)), dim3(256), 0, s, L, out, len);
+  PBF_HIP(hipGetLastError());
+  return 0;
+}
+
 }  // namespace pbf
 
 using namespace pbf;
@@ -1168,23 +1212,12 @@ struct Prover {
   // Horner from the top coefficient over p of L >= 2 coefficients (k_hs1..3): q = the quotient
   // of (p - y) / (x - z) (L - 1 coefficients), *rem = p(z) - y
   int synth_div_run(const uint64_t* p, uint64_t L, const U256& z, const U256& y, uint64_t* q, uint64_t* rem) {
-    const uint64_t nb = (L + HS_BLK - 1) / HS_BLK;
-    DevBuf& hb = ctx->buf("pv.hs");
-    int rc = hb.ensure(nb * 32);
-    if (rc) return rc;
-    uint64_t* totals = (uint64_t*)hb.p;
     HsArgs a;
     a.p = p;
     a.L = L;
     a.y = Fr::from_mont(y);
-    a.z = z;
-    for (int j = 0; j < HS_LOG_T; ++j) a.zs[j] = hpow64(z, (uint64_t)HS_PER << j);
-    hipLaunchKernelGGL(k_hs1, dim3((uint32_t)nb), dim3(HS_T), 0, s, a, q, totals, rem);
-    const U256 zb = hpow64(z, HS_BLK);
-    hipLaunchKernelGGL(k_hs2, dim3(1), dim3(HS_T), 0, s, totals, nb, zb, hpow64(zb, (nb + HS_T - 1) / HS_T));
-    hipLaunchKernelGGL(k_hs3, dim3((uint32_t)nb), dim3(HS_T), 0, s, q, L, a, (const uint64_t*)totals, rem);
-    PBF_HIP(hipGetLastError());
-    return 0;
+    hs_set_point(a, z);
+    return hs_div_run(ctx, a, q, rem, s);
   }
   // q = (p - y) / (x - z) for p of L coefficients; a nonzero remainder fails with `err`
   int synth_div(const uint64_t* p, uint64_t L, const U256& z, const U256& y, uint64_t* q, const char* err) {

@@ -118,6 +118,13 @@ SIGNATURES = [
                                                    _vp]),
     ("pbf_ntt_fr256_coset", ctypes.c_int, [_vp, _p64, _p64, _p64, _sz, _p64, _sz, ctypes.c_int]),
     ("pbf_ntt_fr256_coset_batch_dev", ctypes.c_int, [_vp, _p64, _p64, _vp, _sz, _vp, _sz, _sz, ctypes.c_int, _vp]),
+    ("pbf_poly_eval_fr256", ctypes.c_int, [_vp, _p64, _sz, _p64, _sz, _p64]),
+    ("pbf_kzg_commit_bn254", ctypes.c_int, [_vp, _p64, _sz, _p64, _sz, _sz, _sz, _p64]),
+    ("pbf_kzg_commit_bn254_dev", ctypes.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _p64, _vp]),
+    ("pbf_kzg_open_bn254", ctypes.c_int, [_vp, _p64, _sz, _p64, _sz, _sz, _sz, _p64, _p64, _p64, _p64]),
+    ("pbf_kzg_open_bn254_dev", ctypes.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _p64, _p64, _p64, _p64, _vp]),
+    ("pbf_kzg_verify_bn254", ctypes.c_int, [_vp, _p64, _sz, _p64, _p64, _p64, _p64, _p64,
+                                            ctypes.POINTER(ctypes.c_int)]),
 ]
 
 _lib = None
@@ -492,6 +499,83 @@ class Context:
                                                          ctypes.byref(ok), oe, stream))
         return (ok.value == 1, [bool(v) for v in oe[:count]]) if each else ok.value == 1
 
+    # ---- KZG commitments over BN254 (include/pbf.h "KZG commitments"; kzg.hip)
+    def poly_eval_fr(self, coeffs, xs) -> list:
+        """Poly::eval (poly.rs:71-79) over Fr: [p(x) for x in xs], ints in and out."""
+        c, x = ints_to_limbs(coeffs), ints_to_limbs(xs)
+        y = np.zeros(4 * len(xs), dtype=np.uint64)
+        _check(self.lib.pbf_poly_eval_fr256(self.h, _ptr(c), len(coeffs), _ptr(x), len(xs), _ptr(y)))
+        return limbs_to_ints(y)
+
+    @staticmethod
+    def _poly_limbs(polys, pitch):
+        """A list of equal-length coefficient lists as one limb array, polynomial b at b * pitch."""
+        batch = len(polys)
+        ln = len(polys[0]) if batch else 0
+        if any(len(p) != ln for p in polys):
+            raise ValueError("the polynomials of one call have one length")
+        pitch = ln if pitch is None else int(pitch)
+        a = np.zeros(4 * max(pitch, ln) * max(batch, 1), dtype=np.uint64)
+        for b, p in enumerate(polys):
+            a[4 * b * pitch:4 * (b * pitch + ln)] = ints_to_limbs(p)
+        return a, ln, pitch, batch
+
+    @staticmethod
+    def _points(out) -> list:
+        v = limbs_to_ints(out)
+        return [(v[2 * i], v[2 * i + 1]) for i in range(len(v) // 2)]
+
+    def kzg_commit(self, srs, polys, pitch: int | None = None) -> list:
+        """SRS::eval_at_s (plonk.rs:51-58) of each polynomial (lists of ints of one length);
+        points as (x, y), the identity (0, 0)."""
+        a, ln, pitch, batch = self._poly_limbs(polys, pitch)
+        out = np.zeros(8 * max(batch, 1), dtype=np.uint64)
+        _check(self.lib.pbf_kzg_commit_bn254(self.h, _ptr(_g1_limbs(srs)), len(srs), _ptr(a), ln, pitch, batch,
+                                             _ptr(out)))
+        return self._points(out)[:batch]
+
+    def kzg_commit_dev(self, d_srs: int, srs_m: int, d_polys: int, length: int, pitch: int, batch: int,
+                       stream: int = 0) -> list:
+        out = np.zeros(8 * max(batch, 1), dtype=np.uint64)
+        _check(self.lib.pbf_kzg_commit_bn254_dev(self.h, _vp(d_srs), srs_m, _vp(d_polys), length, pitch, batch,
+                                                 _ptr(out), _vp(stream) if stream else None))
+        return self._points(out)[:batch]
+
+    def kzg_open(self, srs, polys, z: int, weights, pitch: int | None = None):
+        """The batched opening at z: ([p_b(z)], W) with W the commitment of
+        (sum_b weights_b (p_b(x) - p_b(z))) / (x - z) (plonk.rs:429-446)."""
+        a, ln, pitch, batch = self._poly_limbs(polys, pitch)
+        ys = np.zeros(4 * max(batch, 1), dtype=np.uint64)
+        w = np.zeros(8, dtype=np.uint64)
+        _check(self.lib.pbf_kzg_open_bn254(self.h, _ptr(_g1_limbs(srs)), len(srs), _ptr(a), ln, pitch, batch,
+                                           _ptr(ints_to_limbs([z])), _ptr(ints_to_limbs(list(weights))), _ptr(ys),
+                                           _ptr(w)))
+        return limbs_to_ints(ys)[:batch], self._points(w)[0]
+
+    def kzg_open_dev(self, d_srs: int, srs_m: int, d_polys: int, length: int, pitch: int, batch: int, z: int,
+                     weights, stream: int = 0):
+        ys = np.zeros(4 * max(batch, 1), dtype=np.uint64)
+        w = np.zeros(8, dtype=np.uint64)
+        _check(self.lib.pbf_kzg_open_bn254_dev(self.h, _vp(d_srs), srs_m, _vp(d_polys), length, pitch, batch,
+                                               _ptr(ints_to_limbs([z])), _ptr(ints_to_limbs(list(weights))),
+                                               _ptr(ys), _ptr(w), _vp(stream) if stream else None))
+        return limbs_to_ints(ys)[:batch], self._points(w)[0]
+
+    def kzg_verify(self, g2s, entries, rhos) -> bool:
+        """pbf_kzg_verify_bn254: entries a list of (C, z, y, W); rhos the batching weights: nonzero,
+        < r, chosen unpredictably after seeing the openings (soundness rests on that;
+        include/pbf.h). One pairing check whatever the count."""
+        if len(entries) != len(rhos):
+            raise ValueError("one rho per entry")
+        ok = ctypes.c_int(-1)
+        _check(self.lib.pbf_kzg_verify_bn254(self.h, _ptr(_g2_limbs(g2s)), len(entries),
+                                             _ptr(_g1_limbs([e[0] for e in entries])),
+                                             _ptr(ints_to_limbs([e[1] for e in entries])),
+                                             _ptr(ints_to_limbs([e[2] for e in entries])),
+                                             _ptr(_g1_limbs([e[3] for e in entries])),
+                                             _ptr(ints_to_limbs(list(rhos))), ctypes.byref(ok)))
+        return ok.value == 1
+
     def plonk_prove_bn254_sharded_dev(self, comm: "Comm", n, d_q, d_copies, d_abc, chal, rnd, d_srs, srs_m,
                                       k1k2=(2, 3), mode=0, stream: int = 0):
         """This rank's part of the multi-GPU prove (include/pbf.h); comm: a Comm struct."""
@@ -612,6 +696,16 @@ def _g1_limbs(pts) -> np.ndarray:
 
 def _g2_limbs(pts) -> np.ndarray:
     return ints_to_limbs([c for p in pts for c in ((0, 0, 0, 0) if p is None else (p[0][0], p[0][1], p[1][0], p[1][1]))])
+
+
+def kzg_fold(commits, ys, weights, ctx: "Context | None" = None):
+    """A batched opening as one verifier entry: (sum_b w_b C_b, sum_b w_b y_b mod r) for the
+    commitments C_b, claimed evaluations y_b and the opening's weights w_b; with the opening's z
+    and W it is one (C, z, y, W) entry of Context.kzg_verify. The point sum is an MSM (msm_g1)."""
+    if not (len(commits) == len(ys) == len(weights)):
+        raise ValueError("one evaluation and one weight per commitment")
+    c = (ctx or default_context()).msm_g1(list(commits), [int(w) % BN254_R for w in weights])
+    return c, sum(int(w) * int(y) for w, y in zip(weights, ys)) % BN254_R
 
 
 def ints_to_limbs(values) -> np.ndarray:

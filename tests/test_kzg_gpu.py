@@ -1,0 +1,423 @@
+"""KZG commitments over BN254 (csrc/kzg.hip): commit, the batched opening, verification and
+Poly::eval over Fr, bit-exact against Python integers -- no tolerance anywhere.
+
+Expected values use the trapdoor S of the test SRS, so they cost O(len) big-integer work and do not
+depend on the GPU's MSM: commit(p) = p(S) G, y_b = p_b(z), W = ((sum_b w_b (p_b(S) - y_b)) / (S - z)) G.
+One small case also pins the quotient's coefficients through msm_naive over a Python synthetic
+division.
+
+Shapes: the opening evaluates g = 12 polynomials per launch and sums 10 inputs per launch (the
+first launch 10 polynomials, each later one the sum so far and 9 more), so the batches are 1, 2, 3,
+6 and 9, 10, 11, 12, 13, 19, 20, 21, 25 (g - 1, g, g + 1, 2g + 1 for both group sizes, and the
+second group boundary of the sum); the division works in blocks of B = 4096 coefficients (HS_BLK)
+and the evaluation in chunks of 16384, the sizes the lens surround."""
+import ctypes
+import os
+import random
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "plonk-by-fingers_amd"))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+
+import bn254 as F  # noqa: E402
+import bn254_pairing as B  # noqa: E402
+import plonk_bn254 as P  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+R = F.R
+S = 0x1D0C5A11E5EED5A17ED5EC2E7000000000000000000000000000000C0FFEE % R  # the trapdoor
+M = 40000       # device SRS: M + 1 points
+M_HOST = 4100   # host SRS: M_HOST + 1 points
+
+
+def enc(p):
+    return (0, 0) if p is None else p
+
+
+def inv(a):
+    return pow(a % R, R - 2, R)
+
+
+class World:
+    def __init__(self, ctx):
+        import torch
+
+        self.ctx, self.torch = ctx, torch
+        self.d_srs = torch.empty(8 * (M + 1), dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        ctx.srs_create_dev(S, M, self.d_srs.data_ptr())
+        torch.cuda.synchronize()
+        self.srs = ctx.srs_create(S, M_HOST)
+        self.g2s = [B.G2_GEN, ctx.g2_bn254_mul([B.G2_GEN], [S])[0]]
+        self._polys = {}
+
+    def polys(self, ln, batch, pitch, seed):
+        """(limb array of batch * pitch elements, [coefficient lists]) -- random canonical values,
+        the gaps between polynomials filled too (they must not be read)."""
+        key = (ln, batch, pitch, seed)
+        if key not in self._polys:
+            a = F.random_limbs(batch * pitch, seed)
+            ints = F.limbs_to_ints(a)
+            self._polys[key] = (a, [ints[b * pitch:b * pitch + ln] for b in range(batch)])
+        return self._polys[key]
+
+    def dev(self, a):
+        return self.torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
+
+
+@pytest.fixture(scope="module")
+def world(ctx):
+    return World(ctx)
+
+
+def expect_open(polys, z, weights):
+    ys = [F.poly_eval(p, z) for p in polys]
+    num = sum(w * (F.poly_eval(p, S) - y) for w, p, y in zip(weights, polys, ys)) % R
+    return ys, enc(F.g1_mul(F.G1_GEN, num * inv(S - z) % R))
+
+
+def expect_commit(p):
+    return enc(F.g1_mul(F.G1_GEN, F.poly_eval(p, S)))
+
+
+def pick_z(kind, rng, polys=None):
+    if kind == "0":
+        return 0
+    if kind == "1":
+        return 1
+    if kind == "r-1":
+        return R - 1
+    if kind == "root16":
+        return F.root_of_unity(1 << 16)
+    return rng.randrange(R)
+
+
+def pick_weights(kind, batch, rng):
+    if kind == "ones":
+        return [1] * batch
+    w = [rng.randrange(R) for _ in range(batch)]
+    if kind == "zero":
+        w[rng.randrange(batch)] = 0
+    return w
+
+
+LENS = [1, 2, 3, 15, 16, 17, 4095, 4096, 4097, 8193, 16383, 16384, 16385, 40000]
+BATCHES = [1, 2, 3, 6, 9, 10, 11, 12, 13, 19, 20, 21, 25]
+ZK = ["rand", "0", "1", "r-1", "root16"]
+WK = ["rand", "ones", "zero"]
+# every len with batches cycling through the list, then every batch at two lens on either side
+# of a block boundary; z and weight kinds cycle through all of it
+SHAPES = [(ln, BATCHES[(i * 3 + 1) % 13]) for i, ln in enumerate(LENS)]
+SHAPES += [(4097, b) for b in BATCHES] + [(17, b) for b in BATCHES]
+SHAPES = [(ln, b, ZK[i % 5], WK[i % 3]) for i, (ln, b) in enumerate(SHAPES)]
+
+
+@pytest.mark.parametrize("ln,batch,zk,wk", SHAPES, ids=[f"len{s[0]}-b{s[1]}-z{s[2]}-w{s[3]}" for s in SHAPES])
+def test_open_dev_shapes(ctx, world, ln, batch, zk, wk):
+    rng = random.Random(ln * 131 + batch)
+    a, polys = world.polys(ln, batch, ln, 7000 + ln)
+    z = pick_z(zk, rng)
+    weights = pick_weights(wk, batch, rng)
+    d = world.dev(a)
+    ys, w = ctx.kzg_open_dev(world.d_srs.data_ptr(), M + 1, d.data_ptr(), ln, ln, batch, z, weights)
+    want_ys, want_w = expect_open(polys, z, weights)
+    assert ys == want_ys
+    assert w == want_w
+
+
+@pytest.mark.parametrize("ln,batch", [(1, 2), (17, 3), (4097, 2), (16385, 1), (40000, 2)])
+def test_commit_dev(ctx, world, ln, batch):
+    pitch = ln + 5
+    a, polys = world.polys(ln, batch, pitch, 8000 + ln)
+    d = world.dev(a)
+    got = ctx.kzg_commit_dev(world.d_srs.data_ptr(), M + 1, d.data_ptr(), ln, pitch, batch)
+    assert got == [expect_commit(p) for p in polys]
+
+
+def test_pitch_larger_than_len(ctx, world):
+    ln, batch, pitch = 4097, 7, 4097 + 33
+    a, polys = world.polys(ln, batch, pitch, 8100)
+    d = world.dev(a)
+    rng = random.Random(81)
+    z, weights = rng.randrange(R), [rng.randrange(R) for _ in range(batch)]
+    ys, w = ctx.kzg_open_dev(world.d_srs.data_ptr(), M + 1, d.data_ptr(), ln, pitch, batch, z, weights)
+    assert (ys, w) == expect_open(polys, z, weights)
+
+
+def test_quotient_coefficients_against_synthetic_division(ctx, world):
+    """len = 8, batch = 3: W against msm_naive over the quotient's coefficients from a Python
+    synthetic division -- the coefficients themselves, not only the quotient's value at S."""
+    rng = random.Random(83)
+    polys = [[rng.randrange(R) for _ in range(8)] for _ in range(3)]
+    z, weights = rng.randrange(R), [rng.randrange(R) for _ in range(3)]
+    ys, w = ctx.kzg_open(world.srs[:8], polys, z, weights)
+    assert ys == [F.poly_eval(p, z) for p in polys]
+    c = [sum(wb * p[j] for wb, p in zip(weights, polys)) % R for j in range(8)]
+    c[0] = (c[0] - sum(wb * y for wb, y in zip(weights, ys))) % R
+    q, s = [0] * 7, 0
+    for j in range(7, 0, -1):
+        s = (c[j] + z * s) % R
+        q[j - 1] = s
+    assert (c[0] + z * s) % R == 0  # the remainder
+    assert w == enc(F.msm_naive(world.srs[:7], q))
+    assert ctx.kzg_commit(world.srs[:8], polys) == [enc(F.msm_naive(world.srs[:8], p)) for p in polys]
+
+
+def _poly_with_root(rng, ln, a):
+    """(x - a) * (random polynomial of ln - 1 coefficients)"""
+    g = [rng.randrange(R) for _ in range(ln - 1)]
+    p = [0] * ln
+    for i, gi in enumerate(g):
+        p[i] = (p[i] - a * gi) % R
+        p[i + 1] = (p[i + 1] + gi) % R
+    return p
+
+
+@pytest.mark.parametrize("ln", [33, 4100])
+def test_open_special_values(ctx, world, ln):
+    rng = random.Random(9000 + ln)
+    srs = world.srs[:ln]
+    rnd = lambda: [rng.randrange(R) for _ in range(ln)]  # noqa: E731
+    # z a root of p_0: y_0 = 0 and nothing fails
+    a = rng.randrange(R)
+    polys = [_poly_with_root(rng, ln, a), rnd()]
+    ys, w = ctx.kzg_open(srs, polys, a, [3, 5])
+    assert ys[0] == 0 and (ys, w) == expect_open(polys, a, [3, 5])
+    # z on an NTT domain, z = 0, 1, r - 1; a weight of 0, all weights 1
+    for z, weights in ((F.root_of_unity(64), [1, 1]), (0, [0, 7]), (1, [rng.randrange(R), 0]), (R - 1, [1, 1])):
+        assert ctx.kzg_open(srs, polys, z, weights) == expect_open(polys, z, weights), (z, weights)
+    # every coefficient r - 1, with z = r - 1 and weights r - 1
+    top = [[R - 1] * ln] * 3
+    assert ctx.kzg_open(srs, top, R - 1, [R - 1] * 3) == expect_open(top, R - 1, [R - 1] * 3)
+    assert ctx.kzg_commit(srs, top[:1]) == [expect_commit(top[0])]
+    # un-normalised polynomials: trailing zero coefficients
+    short = [rnd()[:ln // 2] + [0] * (ln - ln // 2), [rng.randrange(R)] + [0] * (ln - 1)]
+    z = rng.randrange(R)
+    assert ctx.kzg_open(srs, short, z, [2, 9]) == expect_open(short, z, [2, 9])
+    assert ctx.kzg_commit(srs, short) == [expect_commit(p) for p in short]
+    # the all-zero polynomial: C = W = the identity, y = 0
+    zero = [[0] * ln]
+    assert ctx.kzg_commit(srs, zero) == [(0, 0)]
+    assert ctx.kzg_open(srs, zero, z, [rng.randrange(R)]) == ([0], (0, 0))
+    # a constant: the quotient is empty
+    assert ctx.kzg_open(srs[:1], [[5]], z, [4]) == ([5], (0, 0))
+    assert ctx.kzg_open(srs[:1], [[5], [6]], 0, [1, 1]) == ([5, 6], (0, 0))
+
+
+@pytest.mark.parametrize("n", [1, 2, 16384, 16385, 40000])
+def test_poly_eval_fr(ctx, world, n):
+    rng = random.Random(n)
+    _, (coeffs,) = world.polys(n, 1, n, 9100 + n)
+    x = [rng.randrange(R) for _ in range(3)]
+    for xs in ([x[0]], [x[0], x[1]], [x[0], x[0]], [x[0], x[1], x[2]], [x[1], 0, x[1], 1, R - 1]):
+        assert ctx.poly_eval_fr(coeffs, xs) == [F.poly_eval(coeffs, v) for v in xs], len(xs)
+
+
+def test_dev_forms_match_host_forms_on_a_side_stream(ctx, world):
+    torch = world.torch
+    ln, batch, pitch = 4097, 3, 4100
+    a, polys = world.polys(ln, batch, pitch, 9200)
+    rng = random.Random(92)
+    z, weights = rng.randrange(R), [rng.randrange(R) for _ in range(batch)]
+    host_c = ctx.kzg_commit(world.srs, polys)
+    host_o = ctx.kzg_open(world.srs, polys, z, weights)
+    # the host form's own pitch argument
+    assert ctx.kzg_open(world.srs, polys, z, weights, pitch=pitch) == host_o
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        d = world.dev(a)
+        dev_c = ctx.kzg_commit_dev(world.d_srs.data_ptr(), M + 1, d.data_ptr(), ln, pitch, batch, stream=st.cuda_stream)
+        dev_o = ctx.kzg_open_dev(world.d_srs.data_ptr(), M + 1, d.data_ptr(), ln, pitch, batch, z, weights,
+                                 stream=st.cuda_stream)
+    st.synchronize()
+    assert dev_c == host_c == [expect_commit(p) for p in polys]
+    assert dev_o == host_o == expect_open(polys, z, weights)
+
+
+# ---------------------------------------------------------------- verify
+class Openings:
+    """Five valid (C, z, y, W) entries: three single-polynomial openings and two batched ones
+    folded by kzg_fold."""
+
+    def __init__(self, ctx, world):
+        import pbf
+
+        rng = random.Random(95)
+        srs = world.srs[:17]
+        self.entries = []
+        for k in range(3):
+            p = [rng.randrange(R) for _ in range(17)]
+            z = rng.randrange(R)
+            (c,) = ctx.kzg_commit(srs, [p])
+            (y,), w = ctx.kzg_open(srs, [p], z, [1])
+            self.entries.append((c, z, y, w))
+        for k in range(2):
+            polys = [[rng.randrange(R) for _ in range(17)] for _ in range(3)]
+            z, weights = rng.randrange(R), [rng.randrange(R) for _ in range(3)]
+            cs = ctx.kzg_commit(srs, polys)
+            ys, w = ctx.kzg_open(srs, polys, z, weights)
+            c, y = pbf.kzg_fold(cs, ys, weights, ctx)
+            want_c = enc(F.g1_mul(F.G1_GEN, sum(wb * F.poly_eval(p, S) for wb, p in zip(weights, polys)) % R))
+            assert c == want_c and y == sum(wb * yb for wb, yb in zip(weights, ys)) % R
+            self.entries.append((c, z, y, w))
+        self.rng = rng
+
+    def take(self, count):
+        return [self.entries[i % 5] for i in range(count)], [self.rng.randrange(1, R) for _ in range(count)]
+
+
+@pytest.fixture(scope="module")
+def openings(ctx, world):
+    return Openings(ctx, world)
+
+
+@pytest.mark.parametrize("count", [1, 2, 65])
+def test_verify_accepts_valid_entries(ctx, world, openings, count):
+    ents, rhos = openings.take(count)
+    assert ctx.kzg_verify(world.g2s, ents, rhos) is True
+    if count == 1:
+        for e in openings.entries:  # the single check of plonk.rs:641-650
+            assert ctx.kzg_verify(world.g2s, [e], [1]) is True
+
+
+def _tamper(e, kind):
+    c, z, y, w = e
+    if kind == "y":
+        return (c, z, (y + 1) % R, w)
+    if kind == "W":
+        return (c, z, y, enc(F.g1_add(None if w == (0, 0) else w, F.G1_GEN)))
+    if kind == "C":
+        return (enc(F.g1_add(c, F.G1_GEN)), z, y, w)
+    if kind == "z":
+        return (c, (z + 1) % R, y, w)
+    bad = (c[0], (c[1] + 1) % F.Q)
+    assert kind == "off-curve" and not F.g1_on_curve(bad)
+    return (bad, z, y, w)
+
+
+@pytest.mark.parametrize("kind", ["y", "W", "C", "z", "off-curve"])
+def test_verify_rejects_a_tampered_entry(ctx, world, openings, kind):
+    ents, rhos = openings.take(1)
+    assert ctx.kzg_verify(world.g2s, [_tamper(ents[0], kind)], rhos) is False
+    ents, rhos = openings.take(65)  # one bad entry among 65, at the ends and across a wave boundary
+    for pos in (0, 63, 64):
+        bad = list(ents)
+        bad[pos] = _tamper(ents[pos], kind)
+        assert ctx.kzg_verify(world.g2s, bad, rhos) is False, (kind, pos)
+    assert ctx.kzg_verify(world.g2s, ents, rhos) is True
+
+
+def test_verify_accepts_the_identity_as_an_opening(ctx, world):
+    z = 12345
+    (c,) = ctx.kzg_commit(world.srs[:1], [[7]])
+    ys, w = ctx.kzg_open(world.srs[:1], [[7]], z, [1])
+    assert (ys, w) == ([7], (0, 0)) and c == enc(F.g1_mul(F.G1_GEN, 7))
+    assert ctx.kzg_verify(world.g2s, [(c, z, 7, w)], [1]) is True
+    assert ctx.kzg_verify(world.g2s, [(c, z, 7, w), ((0, 0), 5, 0, (0, 0))], [3, 4]) is True
+    assert ctx.kzg_verify(world.g2s, [(c, z, 8, w)], [1]) is False
+
+
+def test_cancelling_errors_pass_equal_weights_and_fail_random_ones(ctx, world, openings):
+    """The documented hazard: y_0 + d and y_1 - d cancel under rho = 1, 1."""
+    (c0, z0, y0, w0), (c1, z1, y1, w1) = openings.entries[0], openings.entries[1]
+    d = 0xD1FF
+    bad = [(c0, z0, (y0 + d) % R, w0), (c1, z1, (y1 - d) % R, w1)]
+    assert ctx.kzg_verify(world.g2s, [bad[0]], [1]) is False
+    assert ctx.kzg_verify(world.g2s, [bad[1]], [1]) is False
+    assert ctx.kzg_verify(world.g2s, bad, [1, 1]) is True
+    rng = random.Random(96)
+    assert ctx.kzg_verify(world.g2s, bad, [rng.randrange(1, R), rng.randrange(1, R)]) is False
+
+
+def test_interoperates_with_the_prover(ctx):
+    """The w_zw_s opening of a paper-mode proof at n = 8 is the KZG entry (z_s, z omega,
+    z_omega_z, w_zw_s)."""
+    n, s = 8, 0xABCDEF0123456789
+    rng = random.Random(97)
+    q, cp, abc = P.mul_gates_circuit(n, 0xBA7C0000 + n)
+    srs = ctx.srs_create(s, n + 3)
+    g2s = [B.G2_GEN, ctx.g2_bn254_mul([B.G2_GEN], [s])[0]]
+    chal = [rng.randrange(R) for _ in range(5)]
+    pts, fields = ctx.plonk_prove_bn254(q, cp, abc, chal, [rng.randrange(R) for _ in range(9)], srs, mode=1)
+    entry = (enc(pts[3]), chal[3] * F.root_of_unity(n) % R, fields[6], enc(pts[8]))
+    assert ctx.kzg_verify(g2s, [entry], [1]) is True
+    assert ctx.kzg_verify(g2s, [entry], [rng.randrange(1, R)]) is True
+    assert ctx.kzg_verify(g2s, [(entry[0], entry[1], (entry[2] + 1) % R, entry[3])], [1]) is False
+
+
+# ---------------------------------------------------------------- errors
+def test_argument_errors_return_einval_and_leave_the_context_usable(ctx, world):
+    import pbf
+
+    lib, h = ctx.lib, ctx.h
+    u64 = lambda n: np.zeros(n, dtype=np.uint64)  # noqa: E731
+    ptr = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))  # noqa: E731
+    srs = pbf._g1_limbs(world.srs[:8])
+    polys, out, one = u64(4 * 16), u64(8 * 4), pbf.ints_to_limbs([1])
+    big = pbf.ints_to_limbs([R])
+    ok = ctypes.c_int(7)
+    g2 = pbf._g2_limbs(world.g2s)
+    bad = []
+    commit = lambda *a: lib.pbf_kzg_commit_bn254(h, *a)  # noqa: E731
+    opn = lambda *a: lib.pbf_kzg_open_bn254(h, *a)  # noqa: E731
+    ver = lambda *a: lib.pbf_kzg_verify_bn254(h, *a)  # noqa: E731
+    w2 = pbf.ints_to_limbs([1, 1])
+    # NULL pointers
+    bad += [commit(None, 8, ptr(polys), 4, 4, 2, ptr(out)), commit(ptr(srs), 8, None, 4, 4, 2, ptr(out)),
+            commit(ptr(srs), 8, ptr(polys), 4, 4, 2, None),
+            lib.pbf_kzg_commit_bn254(None, ptr(srs), 8, ptr(polys), 4, 4, 2, ptr(out)),
+            opn(ptr(srs), 8, ptr(polys), 4, 4, 2, None, ptr(w2), ptr(out), ptr(out)),
+            opn(ptr(srs), 8, ptr(polys), 4, 4, 2, ptr(one), None, ptr(out), ptr(out)),
+            opn(ptr(srs), 8, ptr(polys), 4, 4, 2, ptr(one), ptr(w2), None, ptr(out)),
+            opn(ptr(srs), 8, ptr(polys), 4, 4, 2, ptr(one), ptr(w2), ptr(out), None),
+            ver(None, 1, ptr(out), ptr(one), ptr(one), ptr(out), ptr(one), ctypes.byref(ok)),
+            ver(ptr(g2), 1, ptr(out), ptr(one), ptr(one), ptr(out), ptr(one), None),
+            lib.pbf_poly_eval_fr256(h, None, 4, ptr(one), 1, ptr(out)),
+            lib.pbf_poly_eval_fr256(h, ptr(polys), 4, ptr(one), 1, None)]
+    # len = 0, batch = 0, batch > 2^16, pitch < len, a short SRS
+    bad += [commit(ptr(srs), 8, ptr(polys), 0, 4, 2, ptr(out)), commit(ptr(srs), 8, ptr(polys), 4, 4, 0, ptr(out)),
+            commit(ptr(srs), 8, ptr(polys), 4, 4, (1 << 16) + 1, ptr(out)),
+            commit(ptr(srs), 8, ptr(polys), 4, 3, 2, ptr(out)), commit(ptr(srs), 3, ptr(polys), 4, 4, 2, ptr(out)),
+            opn(ptr(srs), 8, ptr(polys), 0, 4, 2, ptr(one), ptr(w2), ptr(out), ptr(out)),
+            opn(ptr(srs), 8, ptr(polys), 4, 4, 0, ptr(one), ptr(w2), ptr(out), ptr(out)),
+            opn(ptr(srs), 8, ptr(polys), 4, 4, (1 << 16) + 1, ptr(one), ptr(w2), ptr(out), ptr(out)),
+            opn(ptr(srs), 8, ptr(polys), 4, 3, 2, ptr(one), ptr(w2), ptr(out), ptr(out)),
+            opn(ptr(srs), 2, ptr(polys), 4, 4, 2, ptr(one), ptr(w2), ptr(out), ptr(out)),
+            lib.pbf_poly_eval_fr256(h, ptr(polys), 0, ptr(one), 1, ptr(out)),
+            lib.pbf_poly_eval_fr256(h, ptr(polys), 4, ptr(one), 0, ptr(out))]
+    # host scalars >= r; rho = 0; count = 0 and > 2^20
+    wbad = pbf.ints_to_limbs([1, R])
+    zero = pbf.ints_to_limbs([0])
+    bad += [opn(ptr(srs), 8, ptr(polys), 4, 4, 2, ptr(big), ptr(w2), ptr(out), ptr(out)),
+            opn(ptr(srs), 8, ptr(polys), 4, 4, 2, ptr(one), ptr(wbad), ptr(out), ptr(out)),
+            lib.pbf_poly_eval_fr256(h, ptr(polys), 4, ptr(big), 1, ptr(out)),
+            ver(ptr(g2), 1, ptr(out), ptr(big), ptr(one), ptr(out), ptr(one), ctypes.byref(ok)),
+            ver(ptr(g2), 1, ptr(out), ptr(one), ptr(big), ptr(out), ptr(one), ctypes.byref(ok)),
+            ver(ptr(g2), 1, ptr(out), ptr(one), ptr(one), ptr(out), ptr(big), ctypes.byref(ok)),
+            ver(ptr(g2), 1, ptr(out), ptr(one), ptr(one), ptr(out), ptr(zero), ctypes.byref(ok)),
+            ver(ptr(g2), 0, ptr(out), ptr(one), ptr(one), ptr(out), ptr(one), ctypes.byref(ok)),
+            ver(ptr(g2), (1 << 20) + 1, ptr(out), ptr(one), ptr(one), ptr(out), ptr(one), ctypes.byref(ok))]
+    assert bad == [pbf.PBF_EINVAL] * len(bad), bad
+    assert ok.value == 0  # a rejected verify call leaves *ok = 0
+    # the _dev forms check the same things before touching the device pointers
+    d = world.dev(polys)
+    with pytest.raises(pbf.PbfError) as e:
+        ctx.kzg_open_dev(world.d_srs.data_ptr(), M + 1, d.data_ptr(), 4, 3, 2, 1, [1, 1])
+    assert e.value.code == pbf.PBF_EINVAL
+    with pytest.raises(pbf.PbfError) as e:
+        ctx.kzg_commit_dev(world.d_srs.data_ptr(), 3, d.data_ptr(), 4, 4, 2)
+    assert e.value.code == pbf.PBF_EINVAL
+    with pytest.raises(pbf.PbfError) as e:
+        ctx.kzg_open_dev(world.d_srs.data_ptr(), M + 1, d.data_ptr(), 4, 4, 2, R, [1, 1])
+    assert e.value.code == pbf.PBF_EINVAL
+    # and the next valid calls are right
+    rng = random.Random(98)
+    p = [[rng.randrange(R) for _ in range(9)] for _ in range(2)]
+    z, weights = rng.randrange(R), [rng.randrange(R), rng.randrange(R)]
+    assert ctx.kzg_open(world.srs[:8], p, z, weights) == expect_open(p, z, weights)
+    assert ctx.kzg_commit(world.srs[:9], p) == [expect_commit(x) for x in p]
+    assert ctx.poly_eval_fr(p[0], [z]) == [F.poly_eval(p[0], z)]
