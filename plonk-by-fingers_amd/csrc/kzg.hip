@@ -263,9 +263,7 @@ extern "C" int pbf_kzg_open_bn254_dev(pbf_ctx* ctx, const uint64_t* d_srs, size_
   if ((rc = bq.ensure(std::max<size_t>(len - 1, 1) * 32)) || (rc = by.ensure(batch * 32)) ||
       (rc = res.ensure(sizeof(Xyzz))))
     return rc;
-  // A/B build only (PBF_KZG_NO_MSM=1): stop after the sweep and return W = (0,0), so that
-  // scripts/bench_kzg.py can time the sweeps without the MSM
-  const bool with_msm = len > 1 && !env_default_off("PBF_KZG_NO_MSM");
+  const bool with_msm = len > 1;  // a constant polynomial's quotient is empty: W = the identity
   const Affine* tbl = nullptr;  // validated (one stream sync) before the sweep is enqueued
   if (with_msm && (rc = msm_fixed_table(ctx, d_srs, srs_m, s, &tbl))) return rc;
   const U256 zm = Fr::to_mont(u256_from_u64(z));

@@ -6,13 +6,14 @@
 // MSM = Pippenger, window c = 16 (16 windows over the 254-bit scalars):
 //   1. msm_digits: key = (window << 16) | digit per (point, window), digit 0 skipped
 //   2. radix sort of (key, point index) pairs (msm_sort.hpp) -> points grouped by bucket
-//   3. msm_bucket_bounds: [start, end) of every bucket in the sorted order
-//   4. msm_chunk_acc: the sorted list cut into fixed chunks of MSM_CH entries, one thread
-//      per chunk accumulating its runs of equal keys in XYZZ (every thread does the same
-//      number of additions whatever the bucket sizes); runs that cross a chunk boundary
-//      leave partial sums, which a tree join adds up (msm_join_step / msm_join_rest)
+//   3. msm_bucket_bounds4: [start, end) of every bucket in the sorted order
+//   4. msm_chunk_acc_l29r + msm_l29_finish: the sorted list cut into fixed chunks of MSM_CH
+//      entries, one thread per chunk accumulating its runs of equal keys in 29-bit limbs (every
+//      thread does the same number of additions whatever the bucket sizes); runs that cross a
+//      chunk boundary leave partial sums, which a tree join adds up (msm_join_step /
+//      msm_join_rest)
 //   5. bucket reduction sum_b (b + 1) B_b per window as short parallel trees
-//      (msm_fx_cd / msm_fx_subsets / msm_fx_total, see there)
+//      (msm_fx_cd_seq / msm_fx_subsets_q / msm_fx_total_q, see there)
 //   6. host: Horner over the 16 window sums (2^16 steps), one inversion to affine.
 // The result is a group element, so the canonical affine output is unique.
 #include <cstring>
@@ -102,17 +103,9 @@ __global__ void msm_digits16(const uint64_t* scalars, const uint8_t* inf, uint16
   }
 }
 
-__global__ void msm_bucket_bounds(const uint32_t* keys, uint64_t m, uint32_t* start, uint32_t* end, uint32_t sent) {
-  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (uint64_t)gridDim.x * blockDim.x) {
-    const uint32_t k = keys[j];
-    if (k == sent) continue;
-    if (j == 0 || keys[j - 1] != k) start[k] = (uint32_t)j;
-    if (j == m - 1 || keys[j + 1] != k) end[k] = (uint32_t)(j + 1);
-  }
-}
-// The same bounds, four sorted keys per thread from one 16-B load and no grid-stride loop: the
-// loop above kept one load in flight per wave and iteration (~48 dependent iterations per
-// thread at 2^28 entries: latency-bound, ~1.3 TB/s).
+// [start, end) of every bucket in the sorted keys: four keys per thread from one 16-B load and
+// no grid-stride loop (a one-key grid-stride loop kept one load in flight per wave and
+// iteration, ~48 dependent iterations per thread at 2^28 entries: latency-bound, ~1.3 TB/s).
 __global__ void __launch_bounds__(256) msm_bucket_bounds4(const uint32_t* keys, uint64_t m, uint32_t* start,
                                                           uint32_t* end, uint32_t sent) {
   const uint64_t j0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 4;
@@ -138,21 +131,13 @@ __global__ void __launch_bounds__(256) msm_bucket_bounds4(const uint32_t* keys, 
 }
 static void launch_bucket_bounds(const uint32_t* keys, uint64_t m, uint32_t* start, uint32_t* end, uint32_t sent,
                                  hipStream_t s) {
-  if (env_default_off("PBF_MSM_BOUNDS1"))  // read per call: an A/B knob (the grid-stride form)
-    hipLaunchKernelGGL(msm_bucket_bounds, dim3((uint32_t)(((m + 255) / 256) > 16384 ? 16384 : (m + 255) / 256)),
-                       dim3(256), 0, s, keys, m, start, end, sent);
-  else
-    hipLaunchKernelGGL(msm_bucket_bounds4, dim3((uint32_t)((m + 1023) / 1024)), dim3(256), 0, s, keys, m, start, end,
-                       sent);
+  hipLaunchKernelGGL(msm_bucket_bounds4, dim3((uint32_t)((m + 1023) / 1024)), dim3(256), 0, s, keys, m, start, end,
+                     sent);
 }
 
-#ifndef PBF_MSM_CH
-#define PBF_MSM_CH 43
-#endif
-#ifndef PBF_MSM_ACC_WPE
-#define PBF_MSM_ACC_WPE 3
-#endif
-constexpr uint32_t MSM_CH = PBF_MSM_CH;  // sorted entries per accumulation thread
+constexpr uint32_t MSM_CH = 43;  // sorted entries per accumulation thread
+// waves per SIMD the accumulation kernels are held at (_R: the raw-flush form, 140 VGPRs)
+constexpr int MSM_ACC_WPE = 3, MSM_ACC_WPE_R = 3;
 
 struct ChunkPart {
   union {
@@ -167,76 +152,10 @@ struct ChunkPart {
 // (the whole bucket inside the chunk) are written to their bucket. head[t]: the first run
 // if its bucket started in an earlier chunk; tail[t]: the last run if its bucket starts in
 // this chunk and ends in a later one. Buckets with no entry stay zero (ZZ = 0: identity).
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PBF_MSM_ACC_WPE))) msm_chunk_acc(const Affine* pts, const uint32_t* keys, const uint32_t* vals,
-                                                     const uint32_t* start, const uint32_t* end, uint32_t m,
-                                                     Xyzz* buckets, ChunkPart* head, ChunkPart* tail, uint32_t sent,
-                                                     const uint32_t* m_dev, uint32_t* hkey, uint32_t* tkey) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t c0 = t * MSM_CH;
-  if (c0 >= m) return;  // past the chunks of the m-entry list
-  head[t].key = sent;
-  tail[t].key = sent;
-  hkey[t] = sent;
-  tkey[t] = sent;
-  // m_dev: the valid length, known on the device only (counting sort: no sentinel entries)
-  const uint32_t mv = m_dev ? *m_dev : m;
-  if (c0 >= mv) return;
-  const uint32_t c1 = c0 + MSM_CH < mv ? c0 + MSM_CH : mv;
-  uint32_t cur = keys[c0], rs = c0;
-  Xyzz acc = G1::identity();
-  if (cur == sent) return;  // past the valid prefix (zero digits sort last)
-  auto flush = [&](uint32_t re) {
-    const uint32_t bs = start[cur], be = end[cur];
-    if (bs < rs) {  // continues a bucket of an earlier chunk (possibly spanning this one)
-      head[t].acc = acc;
-      head[t].key = cur;
-      hkey[t] = cur;
-    } else if (be > re) {  // starts here, ends in a later chunk
-      tail[t].acc = acc;
-      tail[t].key = cur;
-      tkey[t] = cur;
-    } else {
-      buckets[cur] = acc;
-    }
-  };
-  // the next entry's point and the entry after it's key and index are loaded while the
-  // current addition runs (the point gathers are random: their latency would otherwise stall
-  // every step, and a point's address is known only once its index has arrived)
-  uint32_t k_nx = cur, v_nx = vals[c0];
-  Affine p_nx = pts[v_nx & ~MSM_NEG];
-  uint32_t k_n2 = 0, v_n2 = 0;
-  if (c0 + 1 < c1) k_n2 = keys[c0 + 1], v_n2 = vals[c0 + 1];
-  for (uint32_t j = c0; j < c1; ++j) {
-    const uint32_t k = k_nx, v = v_nx;
-    Affine p = p_nx;
-    if (j + 1 < c1) {
-      k_nx = k_n2;
-      v_nx = v_n2;
-      p_nx = pts[v_nx & ~MSM_NEG];  // a sentinel entry's index is still a valid point
-      if (j + 2 < c1) k_n2 = keys[j + 2], v_n2 = vals[j + 2];
-    }
-    if (k != cur) {
-      flush(j);
-      if (k == sent) return;
-      cur = k;
-      rs = j;
-      acc = G1::identity();
-    }
-    if (v & MSM_NEG) p.y = Fq::sub(u256_zero(), p.y);
-#ifdef PBF_MSM_MUL2CH
-    acc = G1::madd(acc, p);  // A/B build: the two-chain product
-#else
-    acc = G1::madd_tp(acc, p);
-#endif
-  }
-  flush(c1);
-}
-
-// msm_chunk_acc with the accumulator in 29-bit limbs (msm_l29.hpp: no carry folds in the
-// products, ~205 instead of 319 VALU each); same chunking, same flush targets, the bucket
-// sums converted back to the 32-bit Montgomery form at the flush. Default; PBF_MSM_L29=0
-// selects msm_chunk_acc (A/B).
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PBF_MSM_ACC_WPE)))
+// The accumulator is held in 29-bit limbs (msm_l29.hpp: no carry folds in the products, ~205
+// instead of 319 VALU each); the bucket sums are converted back to the 32-bit Montgomery form
+// at the flush. The c = 16 fixed-base form (long runs, rare flushes).
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSM_ACC_WPE)))
 msm_chunk_acc_l29(const Affine* pts, const uint32_t* keys, const uint32_t* vals, const uint32_t* start,
                   const uint32_t* end, uint32_t m, Xyzz* buckets, ChunkPart* head, ChunkPart* tail, uint32_t sent,
                   const uint32_t* m_dev, uint32_t* hkey, uint32_t* tkey) {
@@ -269,6 +188,10 @@ msm_chunk_acc_l29(const Affine* pts, const uint32_t* keys, const uint32_t* vals,
       buckets[cur] = v;
     }
   };
+  // the next entry's point and the entry after it's key and index are loaded while the
+  // current addition runs (the point gathers are random: their latency would otherwise stall
+  // every step, and a point's address is known only once its index has arrived); a sentinel
+  // entry's index is still a valid point
   uint32_t k_nx = cur, v_nx = vals[c0];
   Affine p_nx = pts[v_nx & ~MSM_NEG];
   uint32_t k_n2 = 0, v_n2 = 0;
@@ -299,18 +222,17 @@ msm_chunk_acc_l29(const Affine* pts, const uint32_t* keys, const uint32_t* vals,
   }
   flush(c1);
 }
-// msm_chunk_acc_l29 with the flush deferred (round 4, default; PBF_MSM_RAWFLUSH=0 selects the
-// kernel above): a flush stores the raw 29-bit-limb accumulator (l29::store_raw, 144 B, no
-// products) -- into braw[key] for a run complete in this chunk, head[t].raw / tail[t].raw for
-// a partial -- and msm_l29_finish converts them afterwards. Lanes of a wave reach their run
-// boundaries at different entries; with the conversion (4 products) inside the loop, a wave
-// executed it at every entry where any lane flushed: with ~100 entries per bucket (wide
-// fixed-base windows, the windowed form) that is most entries. hkey[t] / tkey[t]: the key of
-// chunk t's head / tail partial (the sentinel: none), compact for the join and the finish.
-#ifndef PBF_MSM_ACC_WPE_R
-#define PBF_MSM_ACC_WPE_R 3
-#endif
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PBF_MSM_ACC_WPE_R)))
+// msm_chunk_acc_l29 with the flush deferred (the windowed form and fixed-base windows wider than
+// 16 bits, where runs are short): a flush stores the raw 29-bit-limb accumulator (l29::store_raw,
+// 144 B, no products) -- into braw[key] for a run complete in this chunk, head[t].raw /
+// tail[t].raw for a partial -- and msm_l29_finish converts them afterwards. Lanes of a wave reach
+// their run boundaries at different entries; with the conversion (4 products) inside the loop, a
+// wave executed it at every entry where any lane flushed: with ~30-200 entries per bucket that
+// is most entries. The c = 16 fixed-base form (~500+ per bucket) flushes rarely, and the
+// separate conversion pass costs it more than it saves (2^24 points: 32.5 against 32.0 ms).
+// hkey[t] / tkey[t]: the key of chunk t's head / tail partial (the sentinel: none), compact for
+// the join and the finish.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSM_ACC_WPE_R)))
 msm_chunk_acc_l29r(const Affine* pts, const uint32_t* keys, const uint32_t* vals, const uint32_t* start,
                    const uint32_t* end, uint32_t m, uint32_t* braw, ChunkPart* head, ChunkPart* tail, uint32_t sent,
                    const uint32_t* m_dev, uint32_t* hkey, uint32_t* tkey) {
@@ -393,18 +315,6 @@ __global__ void __launch_bounds__(256) msm_l29_finish(const uint32_t* braw, Xyzz
       if (keep(tkey[t])) tail[t].acc = l29::raw_to_xyzz(tail[t].raw);
     }
   }
-}
-static bool msm_l29() {
-  return env_default_on("PBF_MSM_L29");  // read per call: an A/B knob
-}
-// deferred flush conversion: the default where runs are short (the windowed form, fixed-base
-// windows wider than 16 bits: ~30-200 entries per bucket); the c = 16 fixed-base form (~500+
-// per bucket) flushes rarely, and the separate conversion pass costs it more than it saves
-// (2^24 points: 32.5 against 32.0 ms). PBF_MSM_RAWFLUSH=0/1 forces either (A/B).
-static bool msm_rawflush(bool short_runs = true) {
-  const char* e = ab_env("PBF_MSM_RAWFLUSH");  // an A/B knob (PBF_AB build only)
-  if (e && *e) return atoi(e) != 0;
-  return short_runs;
 }
 
 // ---------------------------------------------------------------- fixed-base MSM
@@ -739,19 +649,6 @@ __device__ __forceinline__ Xyzz fx_bucket(uint32_t k, const Xyzz* buckets, const
   return o < e ? G1::add2(tail[o].acc, head[o + 1].acc) : buckets[k];
 }
 
-// Workgroup tree sum of one value per thread (blockDim.x a power of two <= 256) -> *out.
-__device__ __forceinline__ void fx_tree(Xyzz v, Xyzz* out) {
-  __shared__ Xyzz red[256];
-  const uint32_t t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-  for (uint32_t st = blockDim.x / 2; st > 0; st >>= 1) {
-    if (t < st) red[t] = G1::add2(red[t], red[t + st]);
-    __syncthreads();
-  }
-  if (t == 0) *out = red[0];
-}
-
 // Fixed-base bucket reduction T = sum_{b < 2^15} (b + 1) B_b as short parallel trees instead
 // of running sums (the tail is a latency chain: its depth in point additions is its time).
 // With b = 256 h + l (h < 128, l < 256), C_h = sum_l B_(256h+l), D_l = sum_h B_(256h+l):
@@ -762,25 +659,14 @@ __device__ __forceinline__ void fx_tree(Xyzz v, Xyzz* out) {
 // segment running sums and their tree.
 constexpr uint32_t FX_NH = FX_NB / 256;  // 128 values of h
 static_assert(FX_NH == 128, "2^15 buckets = 128 x 256");
-// workgroup (g, w): window w's buckets start at w * 2^15 (keys (w << 15) | b); g < 128: C_g
-// (256 buckets), g >= 128: D_(g-128) (128 buckets); cd holds 384 sums per window
-__global__ void __launch_bounds__(256) msm_fx_cd(const Xyzz* buckets, const ChunkPart* head, const ChunkPart* tail,
-                                                 const uint32_t* start, const uint32_t* end, Xyzz* cd) {
-  const uint32_t g = blockIdx.x, t = threadIdx.x, base = blockIdx.y * FX_NB;
-  Xyzz v;
-  if (g < FX_NH)
-    v = fx_bucket(base + 256 * g + t, buckets, head, tail, start, end);
-  else
-    v = t < FX_NH ? fx_bucket(base + 256 * t + (g - FX_NH), buckets, head, tail, start, end) : G1::identity();
-  fx_tree(v, cd + (uint64_t)blockIdx.y * (FX_NH + 256) + g);
-}
-// The same C_h / D_l sums for many windows at once (the windowed MSM: 16 x 384 trees), where
+// The C_h / D_l sums for many windows at once (the windowed MSM: 16 x 384 trees; window w's
+// buckets start at w * 2^15, keys (w << 15) | b; cd holds 384 sums per window), where
 // throughput matters more than depth: a 256-tree keeps on average a quarter of its lanes
 // busy, so each thread first adds SEQ buckets in sequence. Workgroup (g, w), g < 128 / SEQ:
 // C_h for h = SEQ g .. SEQ g + SEQ - 1 (256 / SEQ threads per h, SEQ consecutive buckets
 // each, then (256 / SEQ)-lane trees); the other 128 / SEQ workgroups: D_l for 2 SEQ values
 // of l each (128 / SEQ threads per l, SEQ values of h each, then (128 / SEQ)-lane trees).
-// SEQ trades depth (SEQ + log2(lanes) additions) against waves in flight (PBF_MSM_CD_SEQ).
+// SEQ trades depth (SEQ + log2(lanes) additions) against waves in flight; launched at SEQ = 8.
 // (Round 3: single-chain products in the sequential part measured no faster, 3.25-3.28 vs
 // 3.25 ms per windowed MSM, profiles/r03/msm_addtp_ab.log: two to four waves per SIMD leave
 // the interleaved products' latency hiding the better trade here.)
@@ -810,39 +696,11 @@ __global__ void __launch_bounds__(256) msm_fx_cd_seq(const Xyzz* buckets, const 
   }
   if (t % lanes == 0) out[g < CG ? SEQ * g + t / CL : FX_NH + 2 * SEQ * (g - CG) + t / DL] = red[t];
 }
-// workgroup (s, w) (128 threads): s < 8: 2^s Y_s; 8 <= s < 15: 2^s Z_(s-8); s = 15: S.
-__global__ void __launch_bounds__(128) msm_fx_subsets(const Xyzz* cd, Xyzz* sub) {
-  const uint32_t s = blockIdx.x, t = threadIdx.x;
-  const Xyzz* C = cd + (uint64_t)blockIdx.y * (FX_NH + 256);
-  const Xyzz* D = C + FX_NH;
-  Xyzz v;
-  if (s < 8) {  // the t-th l with bit s set
-    v = D[((t >> s) << (s + 1)) | (1u << s) | (t & ((1u << s) - 1))];
-  } else if (s < 15) {
-    const uint32_t k = s - 8;
-    v = t < 64 ? C[((t >> k) << (k + 1)) | (1u << k) | (t & ((1u << k) - 1))] : G1::identity();
-  } else {
-    v = C[t];
-  }
-  __shared__ Xyzz res;
-  fx_tree(v, &res);
-  if (t == 0) {
-    Xyzz r = res;
-    const uint32_t e = s < 15 ? s : 0;  // Y_s weight 2^s; Z_k weight 2^(k+8) = 2^s
-    for (uint32_t i = 0; i < e; ++i) r = G1::dbl2(r);
-    sub[blockIdx.y * 16 + s] = r;
-  }
-}
-// workgroup w (16 threads): window w's sum of its 16 scaled subset sums
-__global__ void __launch_bounds__(16) msm_fx_total(const Xyzz* sub, Xyzz* out) {
-  fx_tree(sub[blockIdx.x * 16 + threadIdx.x], out + blockIdx.x);
-}
 
-// ---- the same reduction tail on quads (G1Quad: each point addition's product steps spread
-// over the four lanes of a quad), the default: these kernels are latency chains of a few
-// hundred waves, so a chain of quad additions (one product of latency per step) finishes
-// about 3x sooner than one of single-lane additions (three or four interleaved products per
-// step). PBF_MSM_QUAD=0 restores the single-lane kernels above (A/B).
+// ---- the rest of the reduction tail on quads (G1Quad: each point addition's product steps
+// spread over the four lanes of a quad): these kernels are latency chains of a few hundred
+// waves, so a chain of quad additions (one product of latency per step) finishes about 3x
+// sooner than one of single-lane additions (three or four interleaved products per step).
 __device__ __forceinline__ Xyzz fx_bucket_q(uint32_t k, const Xyzz* buckets, const ChunkPart* head,
                                             const ChunkPart* tail, const uint32_t* start, const uint32_t* end) {
   const uint32_t bs = start[k], be = end[k];
@@ -864,32 +722,16 @@ __device__ __forceinline__ Xyzz fx_tree_q(Xyzz v, Xyzz* red) {
   }
   return v;
 }
-// msm_fx_cd on quads: workgroup (g, w) of 256 threads (64 quads); g < 128: C_g, each quad
-// first adds 4 consecutive buckets; g >= 128: D_(g-128), each quad 2 values of h.
-__global__ void __launch_bounds__(256) msm_fx_cd_q(const Xyzz* buckets, const ChunkPart* head, const ChunkPart* tail,
-                                                   const uint32_t* start, const uint32_t* end, Xyzz* cd) {
-  __shared__ Xyzz red[64];
-  const uint32_t g = blockIdx.x, qi = threadIdx.x >> 2, base = blockIdx.y * FX_NB;
-  Xyzz v = G1::identity();
-  if (g < FX_NH) {
-    for (uint32_t i = 0; i < 4; ++i)
-      v = G1Quad::add(v, fx_bucket_q(base + 256 * g + 4 * qi + i, buckets, head, tail, start, end));
-  } else {
-    for (uint32_t i = 0; i < 2; ++i)
-      v = G1Quad::add(v, fx_bucket_q(base + 256 * (2 * qi + i) + (g - FX_NH), buckets, head, tail, start, end));
-  }
-  v = fx_tree_q(v, red);
-  if (threadIdx.x == 0) cd[(uint64_t)blockIdx.y * (FX_NH + 256) + g] = v;
-}
-// msm_fx_subsets on quads: workgroup (s, w) of 512 threads (128 quads), quad i in the role of
-// thread i there; quad 0 then applies the 2^s weight.
+// The subset sums: workgroup (s, w) of 512 threads (128 quads, one value per quad): s < 8:
+// 2^s Y_s; 8 <= s < 15: 2^s Z_(s-8) (Z_k weight 2^(k+8) = 2^s); s = 15: S. Quad 0 then applies
+// the 2^s weight.
 __global__ void __launch_bounds__(512) msm_fx_subsets_q(const Xyzz* cd, Xyzz* sub) {
   __shared__ Xyzz red[128];
   const uint32_t s = blockIdx.x, t = threadIdx.x >> 2;
   const Xyzz* C = cd + (uint64_t)blockIdx.y * (FX_NH + 256);
   const Xyzz* D = C + FX_NH;
   Xyzz v;
-  if (s < 8) {
+  if (s < 8) {  // the t-th l with bit s set
     v = D[((t >> s) << (s + 1)) | (1u << s) | (t & ((1u << s) - 1))];
   } else if (s < 15) {
     const uint32_t k = s - 8;
@@ -904,32 +746,27 @@ __global__ void __launch_bounds__(512) msm_fx_subsets_q(const Xyzz* cd, Xyzz* su
     if (threadIdx.x == 0) sub[blockIdx.y * 16 + s] = v;
   }
 }
-// msm_fx_total on quads: workgroup w of 64 threads (16 quads)
+// workgroup w of 64 threads (16 quads): window w's sum of its 16 scaled subset sums
 __global__ void __launch_bounds__(64) msm_fx_total_q(const Xyzz* sub, Xyzz* out) {
   __shared__ Xyzz red[16];
   const Xyzz v = fx_tree_q(sub[blockIdx.x * 16 + (threadIdx.x >> 2)], red);
   if (threadIdx.x == 0) out[blockIdx.x] = v;
 }
-static bool msm_quad_tail() {
-  return env_default_on("PBF_MSM_QUAD");  // read per call: an A/B knob
-}
-// the wide-window join: light buckets summed in sequence by the C / D sums, heavy ones by
-// msm_join_chunks (default), or every bucket by the per-bucket steps (=0: A/B). The c = 16 form
-// always takes the per-bucket steps: its spans are even (random scalars: a 14-bit top window),
-// and the per-chunk steps would be a dozen idle launches per MSM on the tail stream.
-static bool fx_chunk_join() {
-  return env_default_on("PBF_MSM_CHUNK_JOIN");  // read per call: an A/B knob
-}
+// The wide-window join (c > 16): light buckets are summed in sequence by msm_fx_resolve, heavy
+// ones by msm_heavy_list / msm_join_heavy, the heaviest by msm_join_chunks. The c = 16 form
+// takes the per-bucket steps (msm_join_step): its spans are even (random scalars: a 14-bit top
+// window), and the per-chunk steps would be a dozen idle launches per MSM on the tail stream.
 constexpr uint32_t FX_JOIN_GROUP_C = 4096;  // per-chunk steps 1 .. 2048, the rest sequential
-constexpr uint32_t FX_SEQ_CAP = 4;  // wide windows: spans <= 4 chunks summed in fx_bucket_into
+constexpr uint32_t FX_SEQ_CAP = 4;  // wide windows: spans <= 4 chunks summed in msm_fx_resolve
 
 // ---- the fixed-base tail for any window width (FxGeom: 2^(lb + hb) buckets, b = 2^lb h + l):
 //   C_h = sum_l B_(2^lb h + l) (2^hb values), D_l = sum_h B_(2^lb h + l) (2^lb values),
 //   T = sum_b (b + 1) B_b = sum_{k < hb} 2^(k + lb) Z_k + sum_{k < lb} 2^k Y_k + S,
 //   Z_k = sum_{h: bit k of h} C_h, Y_k = sum_{l: bit k of l} D_l, S = sum_h C_h
 // (the c = 16 kernels above with 256 -> 2^lb, 128 -> 2^hb). Workgroups of QW quads; every quad
-// first adds its share of the values in sequence, then a quad tree. At c = 16 the sequences
-// and trees are those of msm_fx_cd_q / msm_fx_subsets_q.
+// first adds its share of the values in sequence, then a quad tree. msm_fxg_cd_q is the c = 16
+// form (latency: 384 short trees, QW = 64: 4 consecutive buckets per quad for C_g, 2 values of
+// h for D_l).
 template <int QW>
 __global__ void __launch_bounds__(4 * QW) msm_fxg_cd_q(const Xyzz* buckets, const ChunkPart* head,
                                                        const ChunkPart* tail, const uint32_t* start,
@@ -953,30 +790,11 @@ __global__ void __launch_bounds__(4 * QW) msm_fxg_cd_q(const Xyzz* buckets, cons
   v = fx_tree_q(v, red);
   if (threadIdx.x == 0) cd[g] = v;
 }
-// The C_h / D_l sums of msm_fxg_cd_q on single lanes (wide windows: 2^18 .. 2^21 buckets, a
-// throughput job; a quad addition costs four lanes for one sum): each lane adds per = count /
-// lanes values in sequence, then a `lanes`-lane LDS tree. Workgroup g < gC: C_h for vc = 256 /
-// lc values of h (lc = min(256, L / SEQ) lanes each); then D_l for vd values of l.
-// Bucket k's parts added into acc: its whole sum (buckets[k]) when it lies in one chunk; its
-// chunk-o tail run and its continuations head[o+1 .. e] one by one when it spans at most cap
-// chunks (the wide-window tails skip the join for those: ~2 chunks per bucket); else the tail
-// run and the joined continuations head[o+1].
-__device__ __forceinline__ Xyzz fx_bucket_into(Xyzz acc, uint32_t k, const Xyzz* buckets, const ChunkPart* head,
-                                               const ChunkPart* tail, const uint32_t* start, const uint32_t* end,
-                                               uint32_t cap) {
-  const uint32_t bs = start[k], be = end[k];
-  if (be <= bs) return acc;
-  const uint32_t o = bs / MSM_CH, e = (be - 1) / MSM_CH;
-  if (o == e) return G1::add2(acc, buckets[k]);
-  acc = G1::add2(acc, tail[o].acc);
-  if (e - o > cap) return G1::add2(acc, head[o + 1].acc);
-  for (uint32_t u = o + 1; u <= e; ++u) acc = G1::add2(acc, head[u].acc);
-  return acc;
-}
-// Every bucket spanning chunks resolved to one sum in buckets[k] (one lane per bucket; its tail
-// run plus its continuations as fx_bucket_into adds them): the C and D sums then add one value
-// per bucket each, where each of them added the bucket's ~3 parts (wide windows, ~100 entries
-// per bucket over 43-entry chunks).
+// Every bucket spanning chunks resolved to one sum in buckets[k], one lane per bucket: its
+// chunk-o tail run plus its continuations head[o+1 .. e] one by one when it spans at most cap
+// chunks (the wide-window tail skips the join for those: ~2 chunks per bucket), else the tail
+// run and the joined continuations head[o+1]. The C and D sums then add one value per bucket
+// each (wide windows, ~100 entries per bucket over 43-entry chunks: ~3 parts per bucket).
 __global__ void __launch_bounds__(256) msm_fx_resolve(Xyzz* buckets, const ChunkPart* head, const ChunkPart* tail,
                                                       const uint32_t* start, const uint32_t* end, uint32_t nb,
                                                       uint32_t cap, uint32_t hmax) {
@@ -1001,7 +819,12 @@ __device__ __forceinline__ Xyzz fx_bucket_resolved(Xyzz acc, uint32_t k, const X
                                                    const uint32_t* end) {
   return end[k] <= start[k] ? acc : G1::add2(acc, buckets[k]);
 }
-template <int SEQ, bool RES>
+// The C_h / D_l sums on single lanes over the resolved buckets (wide windows: 2^18 .. 2^21
+// buckets, a throughput job; a quad addition costs four lanes for one sum): each lane adds per =
+// count / lanes values in sequence, then a `lanes`-lane LDS tree. Workgroup g < gC: C_h for vc =
+// 256 / lc values of h (lc = min(256, L / SEQ) lanes each); then D_l for vd values of l.
+// Launched at SEQ = 8. (head, tail and cap are not read: msm_fx_resolve has folded them in.)
+template <int SEQ>
 __global__ void __launch_bounds__(256) msm_fxg_cd_seq(const Xyzz* buckets, const ChunkPart* head,
                                                       const ChunkPart* tail, const uint32_t* start,
                                                       const uint32_t* end, Xyzz* cd, int lb, int hb, uint32_t cap) {
@@ -1014,15 +837,13 @@ __global__ void __launch_bounds__(256) msm_fxg_cd_seq(const Xyzz* buckets, const
   if (g < gC) {
     const uint32_t h = g * vc + t / lc, per = L / lc, l0 = (t % lc) * per;
     for (uint32_t i = 0; i < per; ++i)
-      acc = RES ? fx_bucket_resolved(acc, L * h + l0 + i, buckets, start, end)
-                : fx_bucket_into(acc, L * h + l0 + i, buckets, head, tail, start, end, cap);
+      acc = fx_bucket_resolved(acc, L * h + l0 + i, buckets, start, end);
     lanes = lc;
     outi = h;
   } else {
     const uint32_t l = (g - gC) * vd + t / ld, per = NH / ld, h0 = (t % ld) * per;
     for (uint32_t i = 0; i < per; ++i)
-      acc = RES ? fx_bucket_resolved(acc, L * (h0 + i) + l, buckets, start, end)
-                : fx_bucket_into(acc, L * (h0 + i) + l, buckets, head, tail, start, end, cap);
+      acc = fx_bucket_resolved(acc, L * (h0 + i) + l, buckets, start, end);
     lanes = ld;
     outi = NH + l;
   }
@@ -1174,9 +995,9 @@ static MsmWork msm_work(pbf_ctx* ctx) {
 // (key, value) pairs sorted by key bits [0, bits) into keys2 / vals2 (msm_sort.hpp), with the
 // context's scratch
 static int msm_sort_pairs(pbf_ctx* ctx, const uint32_t* keys, const uint32_t* vals, uint32_t* keys2, uint32_t* vals2,
-                          uint64_t m, int bits, hipStream_t s, const std::string& pre = "msm.") {
+                          uint64_t m, int bits, hipStream_t s) {
   if (m > 0xFFFFFFFFull - RS_TILE_MAX) return fail(PBF_EINVAL, "too many MSM entries");
-  DevBuf &tk = ctx->buf(pre + "sort.k"), &tv = ctx->buf(pre + "sort.v"), &hb = ctx->buf(pre + "sort.hist");
+  DevBuf &tk = ctx->buf("msm.sort.k"), &tv = ctx->buf("msm.sort.v"), &hb = ctx->buf("msm.sort.hist");
   const uint64_t ntiles = (m + RS_TILE - 1) / RS_TILE;
   int rc;
   if ((rc = tk.ensure(m * 4)) || (rc = tv.ensure(m * 4)) || (rc = hb.ensure((256 * ntiles + 256) * 4))) return rc;
@@ -1185,42 +1006,31 @@ static int msm_sort_pairs(pbf_ctx* ctx, const uint32_t* keys, const uint32_t* va
   return 0;
 }
 
-// The MSM sorts with their first pass from planar 16-bit digit codes (dg.dig, m = 16 n entries): (key, value) pairs sorted by the 16-bit (fixed-base) or 20-bit
-// (windowed) key into keys2 / vals2. Pass 1 (bits 0-7) reads the codes, the later passes the
-// ping-pong scratch. Default; PBF_MSM_FUSED_SORT=0 selects the (key, value) pair sort.
-static bool msm_fused_sort() {
-  return env_default_on("PBF_MSM_FUSED_SORT");  // read per call: an A/B knob (=0: pair sort)
-}
-// digit width of pass p of a `bits`-bit sort: as equal as possible (msm_sort.hpp rs_width);
-// PBF_MSM_SORT_W8=1 keeps every pass but the last at 8 bits (A/B)
-static int msm_sort_width(int bits, int p) {
-  if (env_default_off("PBF_MSM_SORT_W8")) {  // read per call: an A/B knob
-    const int rest = bits - 8 * p;
-    return rest < 8 ? rest : 8;
-  }
-  return rs_width(bits, p);
-}
+// The MSM sorts with their first pass from planar digit codes (dg.dig, m = nw n entries): (key,
+// value) pairs sorted by the c-bit (fixed-base) or 20-bit (windowed) key into keys2 / vals2. The
+// first pass reads the codes, the later passes the ping-pong scratch; pass widths as equal as
+// possible (msm_sort.hpp rs_width). Taken where rs_dig_ok(n); smaller n take msm_sort_pairs.
 // bits: key bits to sort (2 or 3 passes; the last lands in keys2 / vals2, the middle one in
 // the caller's mid_k / mid_v buffers, free once the codes are read)
 template <typename C>
 static int msm_sort_digits(pbf_ctx* ctx, const RsDigitsT<C>& dg, uint32_t* keys2, uint32_t* vals2, uint32_t* mid_k,
-                           uint32_t* mid_v, uint64_t m, int bits, hipStream_t s, const std::string& pre = "msm.") {
+                           uint32_t* mid_v, uint64_t m, int bits, hipStream_t s) {
   if (m > 0xFFFFFFFFull - RS_TILE_MAX) return fail(PBF_EINVAL, "too many MSM entries");
-  const int passes = rs_passes(bits), w0 = msm_sort_width(bits, 0);
+  const int passes = rs_passes(bits), w0 = rs_width(bits, 0);
   if (bits < 9 || bits > 24 || dg.kw % (1u << w0) || !rs_dig_ok(dg.n) || (passes == 3 && (!mid_k || !mid_v)))
     return fail(PBF_EINVAL, "digit sort: 9..24 key bits, whole first-pass digits per window, n >= 256");
-  DevBuf &tk = ctx->buf(pre + "sort.k"), &tv = ctx->buf(pre + "sort.v"), &hb = ctx->buf(pre + "sort.hist");
+  DevBuf &tk = ctx->buf("msm.sort.k"), &tv = ctx->buf("msm.sort.v"), &hb = ctx->buf("msm.sort.hist");
   const uint64_t ntiles = (m + RS_TILE - 1) / RS_TILE;
   int rc;
   if ((rc = tk.ensure(m * 4)) || (rc = tv.ensure(m * 4)) || (rc = hb.ensure((256 * ntiles + 256) * 4))) return rc;
   uint32_t *k1 = (uint32_t*)tk.p, *v1 = (uint32_t*)tv.p, *hist = (uint32_t*)hb.p;
   rs_pass<RS_ITEMS, true, C>(nullptr, nullptr, k1, v1, (uint32_t)m, 0, hist, s, dg, w0);
-  const int w1 = msm_sort_width(bits, 1);
+  const int w1 = rs_width(bits, 1);
   if (passes == 2) {
     rs_pass<RS_ITEMS>(k1, v1, keys2, vals2, (uint32_t)m, w0, hist, s, RsDigits{}, w1);
   } else {
     rs_pass<RS_ITEMS>(k1, v1, mid_k, mid_v, (uint32_t)m, w0, hist, s, RsDigits{}, w1);
-    rs_pass<RS_ITEMS>(mid_k, mid_v, keys2, vals2, (uint32_t)m, w0 + w1, hist, s, RsDigits{}, msm_sort_width(bits, 2));
+    rs_pass<RS_ITEMS>(mid_k, mid_v, keys2, vals2, (uint32_t)m, w0 + w1, hist, s, RsDigits{}, rs_width(bits, 2));
   }
   PBF_HIP(hipGetLastError());
   return 0;
@@ -1246,7 +1056,7 @@ static int msm_device(pbf_ctx* ctx, const uint64_t* d_pts, const uint64_t* d_sc,
     return rc;
   hipLaunchKernelGGL(msm_points_to_mont, dim3(grid1(n)), dim3(256), 0, s, d_pts, (Affine*)w.pts.p,
                      (uint8_t*)w.inf.p, n);
-  if (msm_fused_sort() && rs_dig_ok(n)) {
+  if (rs_dig_ok(n)) {
     // 16-bit digit codes in w.keys2 (read by pass 1; only pass 3 writes w.keys2 again)
     hipLaunchKernelGGL(msm_digits16, dim3(grid1(n)), dim3(256), 0, s, d_sc, (const uint8_t*)w.inf.p,
                        (uint16_t*)w.keys2.p, n);
@@ -1273,23 +1083,15 @@ static int msm_device(pbf_ctx* ctx, const uint64_t* d_pts, const uint64_t* d_sc,
   DevBuf &hk = ctx->buf("msm.hkey"), &tk = ctx->buf("msm.tkey"), &braw = ctx->buf("msm.braw");
   if ((rc = hk.ensure((uint64_t)nchunks * 4 + 4)) || (rc = tk.ensure((uint64_t)nchunks * 4 + 4))) return rc;
   PBF_HIP(hipMemsetAsync(w.span.p, 0, 4, s));
-  if (msm_l29() && msm_rawflush()) {
-    if ((rc = braw.ensure((uint64_t)NBT * 144))) return rc;
-    hipLaunchKernelGGL(msm_chunk_acc_l29r, dim3((nchunks + 255) / 256), dim3(256), 0, s, (const Affine*)w.pts.p,
-                       (const uint32_t*)w.keys2.p, (const uint32_t*)w.vals2.p, (const uint32_t*)w.start.p,
-                       (const uint32_t*)w.end.p, (uint32_t)m, (uint32_t*)braw.p, (ChunkPart*)w.head.p,
-                       (ChunkPart*)w.tail.p, MSM_SENTINEL, (const uint32_t*)nullptr, (uint32_t*)hk.p, (uint32_t*)tk.p);
-    hipLaunchKernelGGL(msm_l29_finish, dim3(grid1((uint64_t)NBT + 2ull * nchunks)), dim3(256), 0, s,
-                       (const uint32_t*)braw.p, (Xyzz*)w.buckets.p, (ChunkPart*)w.head.p, (ChunkPart*)w.tail.p,
-                       (const uint32_t*)hk.p, (const uint32_t*)tk.p, (const uint32_t*)w.start.p,
-                       (const uint32_t*)w.end.p, NBT, nchunks, MSM_SENTINEL, 0u);
-  } else {
-    hipLaunchKernelGGL(msm_l29() ? msm_chunk_acc_l29 : msm_chunk_acc, dim3((nchunks + 255) / 256), dim3(256), 0, s,
-                       (const Affine*)w.pts.p, (const uint32_t*)w.keys2.p, (const uint32_t*)w.vals2.p,
-                       (const uint32_t*)w.start.p, (const uint32_t*)w.end.p, (uint32_t)m, (Xyzz*)w.buckets.p,
-                       (ChunkPart*)w.head.p, (ChunkPart*)w.tail.p, MSM_SENTINEL, (const uint32_t*)nullptr,
-                       (uint32_t*)hk.p, (uint32_t*)tk.p);
-  }
+  if ((rc = braw.ensure((uint64_t)NBT * 144))) return rc;
+  hipLaunchKernelGGL(msm_chunk_acc_l29r, dim3((nchunks + 255) / 256), dim3(256), 0, s, (const Affine*)w.pts.p,
+                     (const uint32_t*)w.keys2.p, (const uint32_t*)w.vals2.p, (const uint32_t*)w.start.p,
+                     (const uint32_t*)w.end.p, (uint32_t)m, (uint32_t*)braw.p, (ChunkPart*)w.head.p,
+                     (ChunkPart*)w.tail.p, MSM_SENTINEL, (const uint32_t*)nullptr, (uint32_t*)hk.p, (uint32_t*)tk.p);
+  hipLaunchKernelGGL(msm_l29_finish, dim3(grid1((uint64_t)NBT + 2ull * nchunks)), dim3(256), 0, s,
+                     (const uint32_t*)braw.p, (Xyzz*)w.buckets.p, (ChunkPart*)w.head.p, (ChunkPart*)w.tail.p,
+                     (const uint32_t*)hk.p, (const uint32_t*)tk.p, (const uint32_t*)w.start.p,
+                     (const uint32_t*)w.end.p, NBT, nchunks, MSM_SENTINEL, 0u);
   hipLaunchKernelGGL(msm_max_span, dim3(max_span_groups(NBT)), dim3(256), 0, s, (const uint32_t*)w.start.p,
                      (const uint32_t*)w.end.p, NBT, (uint32_t*)w.span.p);
   const uint64_t mean_span = m / ((uint64_t)NBT * MSM_CH) + 2;
@@ -1301,39 +1103,18 @@ static int msm_device(pbf_ctx* ctx, const uint64_t* d_pts, const uint64_t* d_sc,
   }
   hipLaunchKernelGGL(msm_join_rest, dim3(NBT / 256), dim3(256), 0, s, (ChunkPart*)w.head.p,
                      (const uint32_t*)w.start.p, (const uint32_t*)w.end.p, NBT, (const uint32_t*)w.span.p);
-  {
-    const char* e = ab_env("PBF_MSM_CD_SEQ");  // an A/B knob (PBF_AB build only)
-    const int v = e ? atoi(e) : 8;
-    const int cd_seq = v == 2 || v == 4 || v == 16 ? v : 8;
-    auto* fn = cd_seq == 2 ? msm_fx_cd_seq<2> : cd_seq == 4 ? msm_fx_cd_seq<4> : cd_seq == 16 ? msm_fx_cd_seq<16> : msm_fx_cd_seq<8>;
-    hipLaunchKernelGGL(fn, dim3(256 / cd_seq, MSM_NW), dim3(256), 0, s, (const Xyzz*)w.buckets.p,
-                       (const ChunkPart*)w.head.p, (const ChunkPart*)w.tail.p, (const uint32_t*)w.start.p,
-                       (const uint32_t*)w.end.p, (Xyzz*)w.shares.p);
-  }
-  if (msm_quad_tail()) {
-    hipLaunchKernelGGL(msm_fx_subsets_q, dim3(16, MSM_NW), dim3(512), 0, s, (const Xyzz*)w.shares.p, (Xyzz*)w.parts.p);
-    hipLaunchKernelGGL(msm_fx_total_q, dim3(MSM_NW), dim3(64), 0, s, (const Xyzz*)w.parts.p, (Xyzz*)w.sums.p);
-  } else {
-    hipLaunchKernelGGL(msm_fx_subsets, dim3(16, MSM_NW), dim3(128), 0, s, (const Xyzz*)w.shares.p, (Xyzz*)w.parts.p);
-    hipLaunchKernelGGL(msm_fx_total, dim3(MSM_NW), dim3(16), 0, s, (const Xyzz*)w.parts.p, (Xyzz*)w.sums.p);
-  }
+  constexpr int CD_SEQ = 8;
+  hipLaunchKernelGGL(msm_fx_cd_seq<CD_SEQ>, dim3(256 / CD_SEQ, MSM_NW), dim3(256), 0, s, (const Xyzz*)w.buckets.p,
+                     (const ChunkPart*)w.head.p, (const ChunkPart*)w.tail.p, (const uint32_t*)w.start.p,
+                     (const uint32_t*)w.end.p, (Xyzz*)w.shares.p);
+  hipLaunchKernelGGL(msm_fx_subsets_q, dim3(16, MSM_NW), dim3(512), 0, s, (const Xyzz*)w.shares.p, (Xyzz*)w.parts.p);
+  hipLaunchKernelGGL(msm_fx_total_q, dim3(MSM_NW), dim3(64), 0, s, (const Xyzz*)w.parts.p, (Xyzz*)w.sums.p);
   PBF_HIP(hipGetLastError());
   return 0;
 }
 
-// The 16-window Horner on the device (A/B against msm_finish_host, PBF_MSM_DEVICE_HORNER=1): one
-// lane, 15 x (16 doublings + 1 addition) in sequence -- a latency chain that a GPU lane runs at
-// ~1 Fq product per ~2200 cycles, the host core far faster.
-__global__ void msm_horner_kernel(const Xyzz* sums, Xyzz* out) {
-  if (threadIdx.x != 0) return;
-  Xyzz acc = sums[MSM_NW - 1];
-  for (int w = MSM_NW - 2; w >= 0; --w) {
-    for (int i = 0; i < MSM_C; ++i) acc = G1::dbl(acc);
-    acc = G1::add(acc, sums[w]);
-  }
-  *out = acc;
-}
-
+// The 16-window Horner, on the host: 15 x (16 doublings + 1 addition) in sequence is a latency
+// chain that a GPU lane runs at ~1 Fq product per ~2200 cycles, a host core far faster.
 static void msm_finish_host(const Xyzz* sums, uint64_t* out) {
   Xyzz acc = sums[MSM_NW - 1];
   for (int w = MSM_NW - 2; w >= 0; --w) {
@@ -1455,45 +1236,21 @@ int msm_fixed_lookup(pbf_ctx* ctx, const uint64_t* d_pts, uint64_t n, hipStream_
 int MsmTail::ensure() {
   if (aux) return 0;
   PBF_HIP(hipStreamCreateWithFlags(&aux, hipStreamNonBlocking));
-  PBF_HIP(hipStreamCreateWithFlags(&prep, hipStreamNonBlocking));
   for (int i = 0; i < MSM_TAIL_SLOTS; ++i) {
     PBF_HIP(hipEventCreateWithFlags(&ready[i], hipEventDisableTiming));
     PBF_HIP(hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
   }
-  for (int i = 0; i < MSM_PREP_SLOTS; ++i) {
-    PBF_HIP(hipEventCreateWithFlags(&prep_done[i], hipEventDisableTiming));
-    PBF_HIP(hipEventCreateWithFlags(&prep_free[i], hipEventDisableTiming));
-  }
-  PBF_HIP(hipEventCreateWithFlags(&sc_ready, hipEventDisableTiming));
   return 0;
 }
 MsmTail::~MsmTail() {
   if (!aux) return;
   (void)hipSetDevice(device);
-  if (prep) (void)hipStreamSynchronize(prep);
   (void)hipStreamSynchronize(aux);
-  if (prep) (void)hipStreamDestroy(prep);
   (void)hipStreamDestroy(aux);
   for (int i = 0; i < MSM_TAIL_SLOTS; ++i) {
     if (ready[i]) (void)hipEventDestroy(ready[i]);
     if (done[i]) (void)hipEventDestroy(done[i]);
   }
-  for (int i = 0; i < MSM_PREP_SLOTS; ++i) {
-    if (prep_done[i]) (void)hipEventDestroy(prep_done[i]);
-    if (prep_free[i]) (void)hipEventDestroy(prep_free[i]);
-  }
-  if (sc_ready) (void)hipEventDestroy(sc_ready);
-}
-
-// Opt-in (PBF_MSM_PREP=1): measured in the prover (profiles/r04/prep_ab.log) at 2^20 gates 25.3-26.0
-// ms against 24.8 ms without it, at 2^24 gates 324.8-325.9 against 328.9 ms -- the sort kernels
-// take CU slots from the VALU-bound accumulation they run beside, which slows it by about as
-// much as their own time.
-hipEvent_t msm_scalars_ready(pbf_ctx* ctx, hipStream_t s) {
-  if (!env_default_off("PBF_MSM_PREP")) return nullptr;  // read per call: an A/B knob
-  MsmTail& t = ctx->msm_tail;
-  if (t.ensure() || hipEventRecord(t.sc_ready, s) != hipSuccess) return nullptr;  // one stream then
-  return t.sc_ready;
 }
 
 int msm_fixed_wait(pbf_ctx* ctx, hipStream_t s) {
@@ -1509,13 +1266,19 @@ int msm_fixed_wait(pbf_ctx* ctx, hipStream_t s) {
 // (throughput-bound, the whole chip). On the context's side stream: the boundary join and
 // the bucket reduction (latency-bound chains of a few hundred waves), overlapping whatever
 // the caller enqueues next on `s`.
+// Two forms, by the table's window width c. c = 16 (~500 entries per bucket, even spans): the
+// accumulation converts at the flush, per-bucket join steps, C / D sums on quads. c > 16 (wide
+// windows: ~100 entries per bucket, a narrow top window with a few very heavy buckets): raw
+// flush, the join by span (none up to FX_SEQ_CAP chunks, the heavy list up to HJ_MAX, per-chunk
+// steps beyond), buckets resolved to one sum each, C / D sums on single lanes.
 int msm_fixed_device(pbf_ctx* ctx, const Affine* table, uint64_t n_table, uint64_t first, const uint64_t* d_sc,
-                     uint64_t n, hipStream_t s, Xyzz* d_result, hipEvent_t sc_ready) {
+                     uint64_t n, hipStream_t s, Xyzz* d_result) {
   if (first + n > n_table) return fail(PBF_EINVAL, "fixed-base MSM: range beyond the table");
   auto& fb = ctx->fixed_base;
   if ((const void*)table != fb.table.p || n_table != fb.n || !fb.inf.p)
     return fail(PBF_EINVAL, "fixed-base MSM: not the context's table");
   const FxGeom g = fx_geom_of(fb.c);
+  const bool wide = g.c > 16;
   const uint32_t NB = g.nb;
   const uint64_t m = n * g.nw;  // entries at most (zero digits are skipped)
   MsmTail& tl = ctx->msm_tail;
@@ -1523,33 +1286,16 @@ int msm_fixed_device(pbf_ctx* ctx, const Affine* table, uint64_t n_table, uint64
   if ((rc = tl.ensure())) return rc;
   const int slot = tl.next;
   const std::string pre = "msm.f" + std::to_string(slot) + ".";
-  // digits, sort and bucket bounds: on the prep stream q (after the scalars' event; the sort
-  // buffers of prep slot ps) or on s
-  const bool use_prep = sc_ready != nullptr;
-  const int ps = tl.prep_next;
-  const hipStream_t q = use_prep ? tl.prep : s;
-  const std::string sp = use_prep ? "msm.p" + std::to_string(ps) + "." : std::string("msm.");
-  DevBuf &keys = ctx->buf(sp + "keys"), &vals = ctx->buf(sp + "vals"), &keys2 = ctx->buf(sp + "keys2"),
-         &vals2 = ctx->buf(sp + "vals2");
+  DevBuf &keys = ctx->buf("msm.keys"), &vals = ctx->buf("msm.vals"), &keys2 = ctx->buf("msm.keys2"),
+         &vals2 = ctx->buf("msm.vals2");
   DevBuf &start = ctx->buf(pre + "start"), &end = ctx->buf(pre + "end"), &buckets = ctx->buf(pre + "buckets"),
          &shares = ctx->buf(pre + "shares"), &parts = ctx->buf(pre + "parts"), &head = ctx->buf(pre + "head"),
          &tail = ctx->buf(pre + "tail"), &spb = ctx->buf(pre + "span"), &hk = ctx->buf(pre + "hkey"),
          &tk = ctx->buf(pre + "tkey");
   DevBuf& braw = ctx->buf("msm.braw");  // read only on s (msm_l29_finish), before the tail forks
-  if (use_prep) {
-    PBF_HIP(hipStreamWaitEvent(q, sc_ready, 0));
-    if (tl.prep_used[ps]) {
-      PBF_HIP(hipStreamWaitEvent(q, tl.prep_free[ps], 0));  // its last accumulation has read it
-      if (keys2.bytes < m * 4 || ctx->buf(sp + "sort.k").bytes < m * 4)
-        PBF_HIP(hipEventSynchronize(tl.prep_free[ps]));  // reallocation
-    }
-  }
   // a slot's buffers may still be read by its previous tail: reuse waits for it, reallocation
   // synchronises
-  if (tl.used[slot]) {
-    PBF_HIP(hipStreamWaitEvent(s, tl.done[slot], 0));
-    if (use_prep) PBF_HIP(hipStreamWaitEvent(q, tl.done[slot], 0));
-  }
+  if (tl.used[slot]) PBF_HIP(hipStreamWaitEvent(s, tl.done[slot], 0));
   const uint64_t hbytes = (m / MSM_CH + 1) * sizeof(ChunkPart);
   const uint64_t nshare = (1ull << g.hb) + (1ull << g.lb);
   if ((head.bytes < hbytes || tail.bytes < hbytes || start.bytes < (uint64_t)NB * 4 || hk.bytes < m / MSM_CH * 4 + 8 ||
@@ -1563,56 +1309,45 @@ int msm_fixed_device(pbf_ctx* ctx, const Affine* table, uint64_t n_table, uint64
       (rc = spb.ensure(4)) || (rc = hk.ensure(m / MSM_CH * 4 + 8)) || (rc = tk.ensure(m / MSM_CH * 4 + 8)))
     return rc;
   const uint8_t* inf = (const uint8_t*)fb.inf.p;
-  // ---- digits, sort by bucket, bucket bounds (on q)
+  // ---- digits and the sort by bucket
   if ((uint64_t)g.nw * n_table >= MSM_NEG) return fail(PBF_EINVAL, "fixed-base MSM: table too large");
-  if (msm_fused_sort() && rs_dig_ok(n)) {
+  if (rs_dig_ok(n)) {
     // keys holds the digit codes (2 B per entry at c = 16, else 4 B); for a 3-pass sort keys
     // and vals then take the middle pass (the codes are read by then)
     if (g.c == 16) {
-      hipLaunchKernelGGL((msm_fx_digits_code<uint16_t, 16>), dim3(grid1(n)), dim3(256), 0, q, d_sc, inf, first, n,
+      hipLaunchKernelGGL((msm_fx_digits_code<uint16_t, 16>), dim3(grid1(n)), dim3(256), 0, s, d_sc, inf, first, n,
                          (uint16_t*)keys.p, g.c, g.nw);
       const RsDigits dg{(const uint16_t*)keys.p, (uint32_t)n, (uint32_t)n_table, (uint32_t)first, 0, NB, MSM_NEG};
       rc = msm_sort_digits(ctx, dg, (uint32_t*)keys2.p, (uint32_t*)vals2.p, (uint32_t*)keys.p, (uint32_t*)vals.p, m,
-                           g.c, q, sp);
+                           g.c, s);
     } else {
       auto* dk = g.c == 18 ? msm_fx_digits_code<uint32_t, 18>
                  : g.c == 20 ? msm_fx_digits_code<uint32_t, 20>
                              : msm_fx_digits_code<uint32_t, 22>;
-      hipLaunchKernelGGL(dk, dim3(grid1(n)), dim3(256), 0, q, d_sc, inf, first, n, (uint32_t*)keys.p, g.c, g.nw);
+      hipLaunchKernelGGL(dk, dim3(grid1(n)), dim3(256), 0, s, d_sc, inf, first, n, (uint32_t*)keys.p, g.c, g.nw);
       const RsDigitsT<uint32_t> dg{(const uint32_t*)keys.p, (uint32_t)n, (uint32_t)n_table, (uint32_t)first, 0, NB,
                                    MSM_NEG};
       rc = msm_sort_digits(ctx, dg, (uint32_t*)keys2.p, (uint32_t*)vals2.p, (uint32_t*)keys.p, (uint32_t*)vals.p, m,
-                           g.c, q, sp);
+                           g.c, s);
     }
     if (rc) return rc;
-  } else {
-    hipLaunchKernelGGL(msm_fx_digits, dim3(grid1(n)), dim3(256), 0, q, d_sc, inf, n_table, first, n,
+  } else {  // too few points for whole first-pass digits per window: (key, value) pairs
+    hipLaunchKernelGGL(msm_fx_digits, dim3(grid1(n)), dim3(256), 0, s, d_sc, inf, n_table, first, n,
                        (uint32_t*)keys.p, (uint32_t*)vals.p, g.c, g.nw);
     if ((rc = msm_sort_pairs(ctx, (const uint32_t*)keys.p, (const uint32_t*)vals.p, (uint32_t*)keys2.p,
-                             (uint32_t*)vals2.p, m, g.c, q, sp)))
+                             (uint32_t*)vals2.p, m, g.c, s)))
       return rc;
   }
-  hipLaunchKernelGGL(msm_fx_clear, dim3(NB / 256), dim3(256), 0, q, (uint32_t*)start.p, (uint32_t*)end.p,
+  // ---- bucket bounds
+  hipLaunchKernelGGL(msm_fx_clear, dim3(NB / 256), dim3(256), 0, s, (uint32_t*)start.p, (uint32_t*)end.p,
                      (uint32_t*)spb.p);
-  launch_bucket_bounds((const uint32_t*)keys2.p, m, (uint32_t*)start.p, (uint32_t*)end.p, NB, q);
-  if (use_prep) {
-    PBF_HIP(hipGetLastError());
-    PBF_HIP(hipEventRecord(tl.prep_done[ps], q));
-    PBF_HIP(hipStreamWaitEvent(s, tl.prep_done[ps], 0));
-  }
+  launch_bucket_bounds((const uint32_t*)keys2.p, m, (uint32_t*)start.p, (uint32_t*)end.p, NB, s);
   // ---- accumulation
-  // no bucket memset: msm_fx_cd reads only the buckets the accumulation wrote (fx_bucket)
+  // no bucket memset: the reduction reads only the buckets the accumulation wrote (fx_bucket)
   const uint32_t nchunks = (uint32_t)((m + MSM_CH - 1) / MSM_CH);
-  const bool rawf = msm_l29() && msm_rawflush(g.c > 16);
-  // the wide-window tail converts the partials of buckets spanning <= HJ_MAX chunks as it reads
-  // them (heavy join, resolve); msm_l29_finish only the rest (PBF_MSM_DEFER_CONV=0: all, A/B).
-  // The conditions are those of the tail below: wide windows, chunk join, single-lane C / D
-  // sums, heavy join and resolve all on.
-  const bool defer = rawf && g.c > 16 && fx_chunk_join() && !env_default_off("PBF_MSM_CD_QUAD") &&
-                     env_default_on("PBF_MSM_HEAVY_JOIN") && env_default_on("PBF_MSM_CD_RESOLVE") &&
-                     env_default_on("PBF_MSM_DEFER_CONV");  // read per call: A/B knobs
-  const uint32_t hmax = defer ? HJ_MAX : 0u;
-  if (rawf) {
+  if (wide) {
+    // msm_l29_finish converts only the partials of buckets spanning more than HJ_MAX chunks; the
+    // tail converts the others as it reads them (msm_join_heavy, msm_fx_resolve)
     if ((rc = braw.ensure((uint64_t)NB * 144))) return rc;
     hipLaunchKernelGGL(msm_chunk_acc_l29r, dim3((nchunks + 255) / 256), dim3(256), 0, s, table,
                        (const uint32_t*)keys2.p, (const uint32_t*)vals2.p, (const uint32_t*)start.p,
@@ -1621,69 +1356,53 @@ int msm_fixed_device(pbf_ctx* ctx, const Affine* table, uint64_t n_table, uint64
     hipLaunchKernelGGL(msm_l29_finish, dim3(grid1((uint64_t)NB + 2ull * nchunks)), dim3(256), 0, s,
                        (const uint32_t*)braw.p, (Xyzz*)buckets.p, (ChunkPart*)head.p, (ChunkPart*)tail.p,
                        (const uint32_t*)hk.p, (const uint32_t*)tk.p, (const uint32_t*)start.p, (const uint32_t*)end.p,
-                       NB, nchunks, NB, hmax);
+                       NB, nchunks, NB, HJ_MAX);
   } else {
-    hipLaunchKernelGGL(msm_l29() ? msm_chunk_acc_l29 : msm_chunk_acc, dim3((nchunks + 255) / 256), dim3(256), 0, s,
-                       table, (const uint32_t*)keys2.p, (const uint32_t*)vals2.p, (const uint32_t*)start.p,
+    hipLaunchKernelGGL(msm_chunk_acc_l29, dim3((nchunks + 255) / 256), dim3(256), 0, s, table,
+                       (const uint32_t*)keys2.p, (const uint32_t*)vals2.p, (const uint32_t*)start.p,
                        (const uint32_t*)end.p, (uint32_t)m, (Xyzz*)buckets.p, (ChunkPart*)head.p, (ChunkPart*)tail.p,
                        NB, (const uint32_t*)nullptr, (uint32_t*)hk.p, (uint32_t*)tk.p);
   }
   hipLaunchKernelGGL(msm_max_span, dim3(max_span_groups(NB)), dim3(256), 0, s, (const uint32_t*)start.p,
                      (const uint32_t*)end.p, NB, (uint32_t*)spb.p);
   PBF_HIP(hipGetLastError());
-  if (use_prep) {  // prep slot ps is free once the accumulation has read keys2 / vals2
-    PBF_HIP(hipEventRecord(tl.prep_free[ps], s));
-    tl.prep_used[ps] = true;
-    tl.prep_next = (ps + 1) % MSM_PREP_SLOTS;
-  }
   // ---- the tail, on the side stream
   hipStream_t a = tl.aux;
   PBF_HIP(hipEventRecord(tl.ready[slot], s));
   PBF_HIP(hipStreamWaitEvent(a, tl.ready[slot], 0));
-  // join steps 1 .. FX_JOIN_GROUP / 2 (steps past the largest span exit at once); wider spans
-  // are finished by msm_join_rest. The grid covers the mean span's pair slots (the kernel
-  // strides over the rest).
-  if (g.c > 16 && fx_chunk_join()) {
-    // buckets spanning up to `cap` chunks (twice the mean span, a power of two): the per-bucket
-    // steps; heavier ones: the per-chunk steps up to FX_JOIN_GROUP_C / 2 (both exit at once past
-    // the largest span), then msm_join_rest_g
-    // wide windows (single-lane C / D sums): buckets spanning up to FX_SEQ_CAP chunks are not
-    // joined at all, fx_bucket_into adds their continuations in sequence
-    const bool wide = !(g.c == 16 || env_default_off("PBF_MSM_CD_QUAD"));
-    const uint64_t mean_span = m / ((uint64_t)NB * MSM_CH) + 2;
-    uint32_t cap = 2;
-    while (cap < 2 * mean_span && cap < FX_JOIN_GROUP_C) cap <<= 1;
-    if (wide) cap = FX_SEQ_CAP;
-    // wide windows: the heavy buckets listed and joined in two launches (PBF_MSM_HEAVY_JOIN=0:
-    // the tree steps below, A/B)
-    const bool heavy = wide && env_default_on("PBF_MSM_HEAVY_JOIN");  // read per call: an A/B knob
-    if (heavy) {
-      DevBuf& hl = ctx->buf(pre + "hlist");
-      if (hl.bytes < (uint64_t)NB * 4 + 4 && tl.used[slot]) PBF_HIP(hipEventSynchronize(tl.done[slot]));
-      if ((rc = hl.ensure((uint64_t)NB * 4 + 4))) return rc;
-      uint32_t* cnt = (uint32_t*)hl.p + NB;
-      PBF_HIP(hipMemsetAsync(cnt, 0, 4, a));
-      hipLaunchKernelGGL(msm_heavy_list, dim3(NB / 256), dim3(256), 0, a, (const uint32_t*)start.p,
-                         (const uint32_t*)end.p, NB, cap, HJ_MAX, (uint32_t*)hl.p, cnt);
-      hipLaunchKernelGGL(msm_join_heavy, dim3(1024), dim3(256), 0, a, (ChunkPart*)head.p, (const uint32_t*)hl.p,
-                         (const uint32_t*)cnt, (const uint32_t*)start.p, (const uint32_t*)end.p, (uint32_t)defer);
-    }
-    // (with the heavy join the tree steps take only the buckets spanning more than HJ_MAX chunks
-    // -- skewed scalars -- and exit at once when there are none)
-    const uint32_t jcap = heavy ? HJ_MAX : cap;
-    for (uint32_t step = 1; step < nchunks && step < FX_JOIN_GROUP_C; step <<= 1) {
-      if (step < cap && !wide) {
-        const uint64_t items = (uint64_t)NB * ((mean_span + 2 * step - 1) / (2 * step));
-        hipLaunchKernelGGL(msm_join_step, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0, a, (ChunkPart*)head.p,
-                           (const uint32_t*)start.p, (const uint32_t*)end.p, NB, step, (const uint32_t*)spb.p, cap);
-      }
+  if (wide) {
+    // join: buckets spanning up to FX_SEQ_CAP chunks are not joined at all (msm_fx_resolve adds
+    // their continuations in sequence); up to HJ_MAX chunks: listed and joined in two launches;
+    // beyond (skewed scalars): the per-chunk steps up to FX_JOIN_GROUP_C / 2, which exit at once
+    // when there are none, then msm_join_rest_g
+    DevBuf& hl = ctx->buf(pre + "hlist");
+    if (hl.bytes < (uint64_t)NB * 4 + 4 && tl.used[slot]) PBF_HIP(hipEventSynchronize(tl.done[slot]));
+    if ((rc = hl.ensure((uint64_t)NB * 4 + 4))) return rc;
+    uint32_t* cnt = (uint32_t*)hl.p + NB;
+    PBF_HIP(hipMemsetAsync(cnt, 0, 4, a));
+    hipLaunchKernelGGL(msm_heavy_list, dim3(NB / 256), dim3(256), 0, a, (const uint32_t*)start.p,
+                       (const uint32_t*)end.p, NB, FX_SEQ_CAP, HJ_MAX, (uint32_t*)hl.p, cnt);
+    hipLaunchKernelGGL(msm_join_heavy, dim3(1024), dim3(256), 0, a, (ChunkPart*)head.p, (const uint32_t*)hl.p,
+                       (const uint32_t*)cnt, (const uint32_t*)start.p, (const uint32_t*)end.p, 1u);
+    for (uint32_t step = 1; step < nchunks && step < FX_JOIN_GROUP_C; step <<= 1)
       hipLaunchKernelGGL(msm_join_chunks, dim3((uint32_t)grid1(nchunks)), dim3(256), 0, a, (ChunkPart*)head.p,
                          (const uint32_t*)hk.p, (const uint32_t*)start.p, (const uint32_t*)end.p, nchunks, step,
-                         (const uint32_t*)spb.p, NB, jcap);
-    }
+                         (const uint32_t*)spb.p, NB, HJ_MAX);
     hipLaunchKernelGGL(msm_join_rest_g, dim3(NB / 256), dim3(256), 0, a, (ChunkPart*)head.p, (const uint32_t*)start.p,
                        (const uint32_t*)end.p, NB, (const uint32_t*)spb.p, FX_JOIN_GROUP_C);
+    // C / D sums: every spanning bucket resolved to one sum, then single lanes (throughput:
+    // 2^18 .. 2^21 buckets)
+    constexpr int CD_SEQ = 8;
+    hipLaunchKernelGGL(msm_fx_resolve, dim3(NB / 256), dim3(256), 0, a, (Xyzz*)buckets.p, (const ChunkPart*)head.p,
+                       (const ChunkPart*)tail.p, (const uint32_t*)start.p, (const uint32_t*)end.p, NB, FX_SEQ_CAP,
+                       HJ_MAX);
+    hipLaunchKernelGGL(msm_fxg_cd_seq<CD_SEQ>, dim3(fxg_cd_seq_groups(g, CD_SEQ)), dim3(256), 0, a,
+                       (const Xyzz*)buckets.p, (const ChunkPart*)head.p, (const ChunkPart*)tail.p,
+                       (const uint32_t*)start.p, (const uint32_t*)end.p, (Xyzz*)shares.p, g.lb, g.hb, FX_SEQ_CAP);
   } else {
+    // join: per-bucket steps 1 .. FX_JOIN_GROUP / 2 (steps past the largest span exit at once);
+    // wider spans are finished by msm_join_rest. The grid covers the mean span's pair slots (the
+    // kernel strides over the rest).
     const uint64_t mean_span = m / ((uint64_t)NB * MSM_CH) + 2;
     for (uint32_t step = 1; step < nchunks && step < FX_JOIN_GROUP; step <<= 1) {
       const uint64_t items = (uint64_t)NB * ((mean_span + 2 * step - 1) / (2 * step));
@@ -1692,41 +1411,15 @@ int msm_fixed_device(pbf_ctx* ctx, const Affine* table, uint64_t n_table, uint64
     }
     hipLaunchKernelGGL(msm_join_rest, dim3(NB / 256), dim3(256), 0, a, (ChunkPart*)head.p, (const uint32_t*)start.p,
                        (const uint32_t*)end.p, NB, (const uint32_t*)spb.p);
+    // C / D sums on quads (latency: 384 short trees)
+    hipLaunchKernelGGL(msm_fxg_cd_q<64>, dim3((uint32_t)nshare), dim3(256), 0, a, (const Xyzz*)buckets.p,
+                       (const ChunkPart*)head.p, (const ChunkPart*)tail.p, (const uint32_t*)start.p,
+                       (const uint32_t*)end.p, (Xyzz*)shares.p, g.lb, g.hb);
   }
-  if (g.c == 16 && !msm_quad_tail()) {
-    hipLaunchKernelGGL(msm_fx_cd, dim3(FX_NH + 256), dim3(256), 0, a, (const Xyzz*)buckets.p, (const ChunkPart*)head.p,
-                       (const ChunkPart*)tail.p, (const uint32_t*)start.p, (const uint32_t*)end.p, (Xyzz*)shares.p);
-    hipLaunchKernelGGL(msm_fx_subsets, dim3(16), dim3(128), 0, a, (const Xyzz*)shares.p, (Xyzz*)parts.p);
-    hipLaunchKernelGGL(msm_fx_total, dim3(1), dim3(16), 0, a, (const Xyzz*)parts.p, d_result);
-  } else {
-    // C / D sums: quads at c = 16 (latency: 384 short trees), single lanes above (throughput:
-    // 2^18 .. 2^21 buckets); then the subset trees on quads
-    if (g.c == 16 || env_default_off("PBF_MSM_CD_QUAD")) {  // read per call: an A/B knob
-      auto* cd = g.c == 16 ? msm_fxg_cd_q<64> : msm_fxg_cd_q<128>;
-      const uint32_t qw = g.c == 16 ? 64 : 128;
-      hipLaunchKernelGGL(cd, dim3((uint32_t)nshare), dim3(4 * qw), 0, a, (const Xyzz*)buckets.p,
-                         (const ChunkPart*)head.p, (const ChunkPart*)tail.p, (const uint32_t*)start.p,
-                         (const uint32_t*)end.p, (Xyzz*)shares.p, g.lb, g.hb);
-    } else {
-      const uint32_t cap_seq = g.c > 16 && fx_chunk_join() ? FX_SEQ_CAP : 1;
-      // resolve the spanning buckets once (default; PBF_MSM_CD_RESOLVE=0: the C and D sums each
-      // add the parts, A/B)
-      const bool res = env_default_on("PBF_MSM_CD_RESOLVE");  // read per call: an A/B knob
-      if (res)
-        hipLaunchKernelGGL(msm_fx_resolve, dim3(NB / 256), dim3(256), 0, a, (Xyzz*)buckets.p, (const ChunkPart*)head.p,
-                           (const ChunkPart*)tail.p, (const uint32_t*)start.p, (const uint32_t*)end.p, NB, cap_seq,
-                           hmax);
-      const bool s32 = env_default_off("PBF_MSM_CD_SEQ32");  // read per call: an A/B knob
-      auto* cdk = s32 ? (res ? msm_fxg_cd_seq<32, true> : msm_fxg_cd_seq<32, false>)
-                      : (res ? msm_fxg_cd_seq<8, true> : msm_fxg_cd_seq<8, false>);
-      hipLaunchKernelGGL(cdk, dim3(fxg_cd_seq_groups(g, s32 ? 32 : 8)), dim3(256), 0, a, (const Xyzz*)buckets.p,
-                         (const ChunkPart*)head.p, (const ChunkPart*)tail.p, (const uint32_t*)start.p,
-                         (const uint32_t*)end.p, (Xyzz*)shares.p, g.lb, g.hb, cap_seq);
-    }
-    hipLaunchKernelGGL(msm_fxg_subsets_q<128>, dim3(g.lb + g.hb + 1), dim3(512), 0, a, (const Xyzz*)shares.p,
-                       (Xyzz*)parts.p, g.lb, g.hb);
-    hipLaunchKernelGGL(msm_fxg_total_q, dim3(1), dim3(128), 0, a, (const Xyzz*)parts.p, g.lb + g.hb + 1, d_result);
-  }
+  // ---- subset trees and the total, on quads
+  hipLaunchKernelGGL(msm_fxg_subsets_q<128>, dim3(g.lb + g.hb + 1), dim3(512), 0, a, (const Xyzz*)shares.p,
+                     (Xyzz*)parts.p, g.lb, g.hb);
+  hipLaunchKernelGGL(msm_fxg_total_q, dim3(1), dim3(128), 0, a, (const Xyzz*)parts.p, g.lb + g.hb + 1, d_result);
   PBF_HIP(hipGetLastError());
   PBF_HIP(hipEventRecord(tl.done[slot], a));
   tl.used[slot] = true;
@@ -1791,17 +1484,6 @@ int pbf_msm_g1_bn254_dev(pbf_ctx* ctx, const uint64_t* d_points, const uint64_t*
   MsmWork w = msm_work(ctx);
   int rc = msm_device(ctx, d_points, d_scalars, n, s, w);
   if (rc) return rc;
-  if (ab_env("PBF_MSM_DEVICE_HORNER")) {  // A/B (PBF_AB build only)
-    DevBuf& res = ctx->buf("msm.horner");
-    if ((rc = res.ensure(sizeof(Xyzz)))) return rc;
-    hipLaunchKernelGGL(msm_horner_kernel, dim3(1), dim3(64), 0, s, (const Xyzz*)w.sums.p, (Xyzz*)res.p);
-    PBF_HIP(hipGetLastError());
-    Xyzz r;
-    PBF_HIP(hipMemcpyAsync(&r, res.p, sizeof(Xyzz), hipMemcpyDeviceToHost, s));
-    PBF_HIP(hipStreamSynchronize(s));
-    xyzz_to_affine_u64(r, out);
-    return PBF_OK;
-  }
   std::vector<Xyzz> sums(MSM_NW);
   PBF_HIP(hipMemcpyAsync(sums.data(), w.sums.p, MSM_NW * sizeof(Xyzz), hipMemcpyDeviceToHost, s));
   PBF_HIP(hipStreamSynchronize(s));

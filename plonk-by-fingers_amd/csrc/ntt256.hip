@@ -1,9 +1,10 @@
 // BN254-Fr NTT and mul_ntt (BASELINE config 3: "Polynomial multiply via NTT,
 // 256-bit scalar field, degree 2^22"). Same Stockham decomposition as the u64 path
 // (ntt_kernels.hpp): P passes of radix R over HBM, an in-LDS Stockham of radix-2^LQ
-// register sub-DFTs per workgroup; elements are 32 B, Montgomery form inside the
-// kernels (canonical at the ABI: converted on the first pass's load and the last
-// pass's store). Replaces fft.rs:66-78 and fft.rs:109-132 for the 256-bit field.
+// register sub-DFTs per workgroup; elements are 32 B, canonical at the ABI and through the
+// passes (the tables are in Montgomery form, see run256); the one-workgroup kernel for
+// n <= 2048 converts at its load and store. Replaces fft.rs:66-78 and fft.rs:109-132 for the
+// 256-bit field.
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -15,12 +16,8 @@
 
 // Product form of the pass kernel's butterflies and twiddles: the single-chain Montgomery
 // product (Fq/Fr::mul_tp: ~17 % fewer VALU per product, carry wait states left to the other
-// waves of a SIMD) by default; -DPBF_NTT256_MUL2CH builds the two-chain form for A/B.
-#ifdef PBF_NTT256_MUL2CH
-#define PBF_FRMUL(a, b) Fr::mul(a, b)
-#else
+// waves of a SIMD).
 #define PBF_FRMUL(a, b) Fr::mul_tp(a, b)
-#endif
 namespace pbf {
 using l29::L29;
 
@@ -32,10 +29,8 @@ struct Pass256 {
   const U256* tw0;     // two-level table (Montgomery)
   const U256* tw1;
   const U256* mul_by;  // last pass (Ns > 1) only, or null: outputs become mont(mul_by[i], y) (mul_ntt)
-  U256 n_inv;          // Montgomery form
   uint64_t n;
   uint32_t log_n, log_ns, tw_bits, blocks_per_poly, batch;
-  uint32_t conv_in, conv_out, scale;
 };
 
 __host__ __device__ constexpr int st_logq(int logr, int s, int lq) {
@@ -102,10 +97,6 @@ __device__ __forceinline__ void stage256(U256* v, U256* lds, const U256* wq, con
 #pragma unroll
       for (int c = 0; c < Q; ++c) v[u * Q + c] = in[(j0 + w) + (uint64_t)(i + c * (R / Q)) * (a.n >> LOGR)];
     }
-    if (a.conv_in) {
-#pragma unroll
-      for (int e = 0; e < PER; ++e) v[e] = Fr::to_mont(v[e]);
-    }
     if (a.log_ns > 0) {
       U256 tw[PER];
       if (a.twpass) {
@@ -164,8 +155,6 @@ __device__ __forceinline__ void stage256(U256* v, U256* lds, const U256* wq, con
       if constexpr (!LAST) {
         lds[r * W + w] = y;
       } else {
-        if (a.scale) y = Fr::mul(y, a.n_inv);
-        if (a.conv_out) y = Fr::from_mont(y);
         if (a.log_ns == 0) {
           lds[w * (R + 1) + r] = y;
         } else {
@@ -467,7 +456,7 @@ __global__ void tw256_fill_kernel(U256* t, const U256* tw0, const U256* tw1, uin
 }
 
 // c = a b / R for canonical a, b (one Montgomery product); the inverse transform that follows
-// (a get_plan256(..., extra_r) plan) puts the R back
+// (a get_plan256(..., extra_r = true) plan) puts the R back
 __global__ void pointwise_mont256_kernel(const U256* a, const U256* b, U256* c, uint64_t count) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (uint64_t)gridDim.x * blockDim.x)
     c[i] = Fr::mul_tp(a[i], b[i]);
@@ -515,10 +504,10 @@ struct Plan256 {
   std::vector<int> logr;
   uint32_t tw_bits = 0;
   U256 n_inv{};
-  bool fold_scale = false;  // inverse: n^-1 folded into the last pass's twiddles (tw1s / its table)
+  // tw1s (inverse plans): tw1 n^-1, for the last pass, which folds the scale into its twiddles
   DevBuf small_tw, tw0, tw1, tw1s;
   std::vector<std::shared_ptr<DevBuf>> rtab, twpass;
-  // the 29-bit-limb passes (option ntt256.l29, default on; multi-pass plans with the scale folded):
+  // the 29-bit-limb passes (option ntt256.l29, default on; multi-pass plans):
   // the same tables as w 2^261 in limbs
   bool l29 = false;
   DevBuf tw0_29, tw1_29, tw1s_29;
@@ -588,14 +577,13 @@ static int make_plan256(const pbf::Options& o, const uint64_t* omega, uint64_t n
   if (rc) return rc;
   // The inverse's n^-1 rides in its last pass's twiddles (every element of a pass with Ns > 1
   // takes one twiddle product, and the pass is linear): tw1s = tw1 n^-1 for the two-level form,
-  // the per-pass table scaled likewise; PBF_NTT256_SCALE_PASS=1 keeps the separate product (A/B).
-  p->fold_scale = inverse && !ab_env("PBF_NTT256_SCALE_PASS");
+  // the per-pass table scaled likewise.
   {
     const U256 step = h_pow(wm, 1ull << p->tw_bits);
     std::vector<U256> t1 = h_powers(step, n >> p->tw_bits);
     rc = up256(p->tw1, t1);
     if (rc) return rc;
-    if (p->fold_scale) {
+    if (inverse) {
       for (auto& x : t1) x = Fr::mul(x, p->n_inv);
       if ((rc = up256(p->tw1s, t1))) return rc;
     }
@@ -609,7 +597,7 @@ static int make_plan256(const pbf::Options& o, const uint64_t* omega, uint64_t n
   for (size_t pi = 0; pi < p->logr.size(); ++pi) {
     const int lr = p->logr[pi];
     const uint64_t R = 1ull << lr;
-    const bool fold = p->fold_scale && pi + 1 == p->logr.size();
+    const bool fold = inverse && pi + 1 == p->logr.size();
     auto rb = std::make_shared<DevBuf>();
     if ((rc = up256(*rb, h_powers(h_pow(wm, n / R), R)))) return rc;
     p->rtab.push_back(rb);
@@ -634,13 +622,13 @@ static int make_plan256(const pbf::Options& o, const uint64_t* omega, uint64_t n
     ns *= R;
     log_ns += lr;
   }
-  // the 29-bit-limb passes' tables (ntt256l_pass_kernel; PBF_NTT256_SCALE_PASS / CONV, A/B
-  // builds only, keep the 32-bit kernel). A converted per-pass table replaces its 32-bit form.
-  p->l29 = o.num("ntt256.l29", 1) != 0 && p->fold_scale == (inverse != 0) && !ab_env("PBF_NTT256_CONV");
+  // the 29-bit-limb passes' tables (ntt256l_pass_kernel). A converted per-pass table replaces its
+  // 32-bit form.
+  p->l29 = o.num("ntt256.l29", 1) != 0;
   if (p->l29) {
     const uint64_t nlo = 1ull << p->tw_bits, nhi = n >> p->tw_bits;
     if ((rc = to29(p->tw0, p->tw0_29, nlo)) || (rc = to29(p->tw1, p->tw1_29, nhi)) ||
-        (p->fold_scale && (rc = to29(p->tw1s, p->tw1s_29, nhi))))
+        (inverse && (rc = to29(p->tw1s, p->tw1s_29, nhi))))
       return rc;
     ns = 1;
     for (size_t pi = 0; pi < p->logr.size(); ++pi) {
@@ -727,7 +715,7 @@ static int run256(const Plan256& p, const U256* d_in, U256* d_out, size_t batch,
       a.rtab = (const L29*)p.rtab29[i]->p;
       a.twpass = (const L29*)p.twpass29[i]->p;
       a.tw0 = (const L29*)p.tw0_29.p;
-      a.tw1 = (const L29*)((p.fold_scale && i == P - 1) ? p.tw1s_29.p : p.tw1_29.p);
+      a.tw1 = (const L29*)((p.inverse && i == P - 1) ? p.tw1s_29.p : p.tw1_29.p);
       a.mul_by = (i == P - 1) ? mul_by : nullptr;
       a.n = p.n;
       a.in_len = (i == 0 && in_len) ? in_len : p.n;
@@ -755,24 +743,17 @@ static int run256(const Plan256& p, const U256* d_in, U256* d_out, size_t batch,
     a.rtab = (const U256*)p.rtab[i]->p;
     a.twpass = (const U256*)p.twpass[i]->p;
     a.tw0 = (const U256*)p.tw0.p;
-    a.tw1 = (const U256*)p.tw1.p;
+    a.tw1 = (const U256*)((p.inverse && i == P - 1) ? p.tw1s.p : p.tw1.p);
     a.mul_by = (i == P - 1) ? mul_by : nullptr;
-    a.n_inv = p.n_inv;
     a.n = p.n;
     a.log_n = p.log_n;
     a.log_ns = log_ns;
     a.tw_bits = p.tw_bits;
     a.blocks_per_poly = (uint32_t)((p.n >> lr) / W);
     a.batch = (uint32_t)batch;
-    // no Montgomery conversions: the twiddles (and n^-1) are stored in Montgomery form, so
-    // mont(x, w R) = x w keeps canonical data canonical through every product, and the adds
-    // are the same in both forms -- the first pass's to_mont and the last pass's from_mont
-    // (one product per element each) are not needed (conv_* kept for A/B: PBF_NTT256_CONV=1)
-    const bool conv = ab_env("PBF_NTT256_CONV") != nullptr;
-    a.conv_in = conv && i == 0;
-    a.conv_out = conv && i == P - 1;
-    a.scale = (p.inverse && i == P - 1 && !p.fold_scale);
-    if (p.fold_scale && i == P - 1) a.tw1 = (const U256*)p.tw1s.p;
+    // no Montgomery conversions: the twiddles (and n^-1, folded into the last pass's) are stored
+    // in Montgomery form, so mont(x, w R) = x w keeps canonical data canonical through every
+    // product, and the adds are the same in both forms
     Pass256Fn fn = pass256_fn(lr);
     if (!fn) return fail(PBF_EINVAL, "no 256-bit kernel for this radix");
     const uint64_t blocks = (uint64_t)a.blocks_per_poly * batch;
@@ -1056,9 +1037,8 @@ int pbf_mul_ntt_fr256(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* a, si
   if (!ctx || !omega || !out || (!a && la) || (!b && lb)) return fail(PBF_EINVAL, "null argument");
   const size_t n = la + lb;
   Plan256 *fw, *iv;
-  const bool mont = !ab_env("PBF_MUL_NTT_TWO_PRODUCTS");  // A/B: to_mont + product, plain inverse
   int rc = get_plan256(ctx, omega, n, 0, &fw);
-  if (!rc) rc = get_plan256(ctx, omega, n, 1, &iv, mont);
+  if (!rc) rc = get_plan256(ctx, omega, n, 1, &iv, true);  // the inverse puts back the product's R
   if (rc) return rc;
   if (!canonical_vec(a, la) || !canonical_vec(b, lb)) return fail(PBF_EINVAL, "input not canonical");
   hipStream_t s = ctx->host_stream();
@@ -1070,8 +1050,7 @@ int pbf_mul_ntt_fr256(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* a, si
   if ((rc = run256(*fw, d, d, 2, ctx->scratch0, ctx->scratch1, s))) return rc;
   uint64_t blocks = (n + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(mont ? pointwise_mont256_kernel : pointwise_mul256_kernel, dim3(blocks), dim3(256), 0, s, d, d + n,
-                     d, (uint64_t)n);
+  hipLaunchKernelGGL(pointwise_mont256_kernel, dim3(blocks), dim3(256), 0, s, d, d + n, d, (uint64_t)n);
   PBF_HIP(hipGetLastError());
   if ((rc = run256(*iv, d, d, 1, ctx->scratch0, ctx->scratch1, s))) return rc;
   PBF_HIP(hipMemcpyAsync(out, d, n * 32, hipMemcpyDeviceToHost, s));
@@ -1085,14 +1064,13 @@ int pbf_mul_ntt_fr256_dev(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* d
                           uint64_t* d_out, size_t n, size_t batch, void* stream) {
   if (!ctx || !omega || !d_a || !d_b || !d_out) return fail(PBF_EINVAL, "null argument");
   Plan256 *fw, *iv;
-  const bool mont = !ab_env("PBF_MUL_NTT_TWO_PRODUCTS");  // A/B: to_mont + product, plain inverse
   int rc = get_plan256(ctx, omega, n, 0, &fw);
-  if (!rc) rc = get_plan256(ctx, omega, n, 1, &iv, mont);
+  if (!rc) rc = get_plan256(ctx, omega, n, 1, &iv, true);  // the inverse puts back the product's R
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  // fused (default past 2048 points): b's forward transform multiplies its last pass's outputs by
-  // a's (already in d_out) and stores the product there; PBF_MUL_NTT_NO_FUSE=1: pointwise kernel
-  if (mont && n > 2048 && !ab_env("PBF_MUL_NTT_NO_FUSE")) {
+  // fused (past 2048 points, the multi-pass plans): b's forward transform multiplies its last
+  // pass's outputs by a's (already in d_out) and stores the product there
+  if (n > 2048) {
     if ((rc = run256(*fw, (const U256*)d_a, (U256*)d_out, batch, ctx->scratch0, ctx->scratch1, s))) return rc;
     if ((rc = run256(*fw, (const U256*)d_b, (U256*)d_out, batch, ctx->scratch0, ctx->scratch1, s, (const U256*)d_out)))
       return rc;
@@ -1104,8 +1082,8 @@ int pbf_mul_ntt_fr256_dev(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* d
   if ((rc = run256(*fw, (const U256*)d_b, fb, batch, ctx->scratch0, ctx->scratch1, s))) return rc;
   uint64_t blocks = (batch * n + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(mont ? pointwise_mont256_kernel : pointwise_mul256_kernel, dim3(blocks), dim3(256), 0, s,
-                     (const U256*)d_out, fb, (U256*)d_out, (uint64_t)(batch * n));
+  hipLaunchKernelGGL(pointwise_mont256_kernel, dim3(blocks), dim3(256), 0, s, (const U256*)d_out, fb,
+                     (U256*)d_out, (uint64_t)(batch * n));
   PBF_HIP(hipGetLastError());
   return run256(*iv, (const U256*)d_out, (U256*)d_out, batch, ctx->scratch0, ctx->scratch1, s);
 }

@@ -141,14 +141,6 @@ __device__ __forceinline__ U256 blk_next_x(const Blk& b, uint64_t p, const U256&
   return Fr::mul_tp(g, fr_pow(w, blk_index(b, p + 64)));
 }
 
-// out[g + G m] = in[g][m] (the all-gathered stride shards of one vector, back in order)
-__global__ void k_interleave(const uint64_t* in, uint64_t* out, uint64_t nl, uint32_t G) {
-  const uint64_t id = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (id >= nl * G) return;
-  const uint64_t g = id / nl, m = id % nl;
-  for (int q = 0; q < 4; ++q) out[4 * (g + G * m) + q] = in[4 * id + q];
-}
-
 // host Montgomery power a^e (a in Montgomery form)
 static U256 h_pow(U256 a, uint64_t e) {
   U256 r = fr_one_m();
@@ -646,8 +638,7 @@ int fr256_scale_pow(bool l29, const uint64_t* in, uint64_t len, uint64_t* out, u
 }
 
 static void launch_quotient(const QuotArgs& qa, uint64_t* out, bool l29, hipStream_t s) {
-  const char* qc = ab_env("PBF_QUOT_CHUNK");
-  const uint32_t qch = qc && atoi(qc) > 0 ? (uint32_t)atoi(qc) : 32;
+  constexpr uint32_t qch = 32;  // points per thread
   const uint32_t blocks = blocks_for((qa.N + qch - 1) / qch);
   if (!l29) {
     hipLaunchKernelGGL(k_quotient, dim3(blocks), dim3(256), 0, s, qa, out, qch);
@@ -1204,10 +1195,8 @@ struct Prover {
   const Affine* srs_tbl = nullptr;
   uint64_t srs_n = 0;
   Xyzz* slots = nullptr;  // 9 (this rank's partial sums when sharded)
-  // ready: msm_scalars_ready recorded after every polynomial of this round's commitments was
-  // complete, so each MSM's digits and sort overlap the previous MSM's accumulation (msm.hpp)
-  int commit(const uint64_t* coeff, uint64_t len, int slot, hipEvent_t ready = nullptr) {
-    return msm_fixed_device(ctx, srs_tbl, srs_n, 0, coeff, len, s, slots + slot, ready);
+  int commit(const uint64_t* coeff, uint64_t len, int slot) {
+    return msm_fixed_device(ctx, srs_tbl, srs_n, 0, coeff, len, s, slots + slot);
   }
   // Horner from the top coefficient over p of L >= 2 coefficients (k_hs1..3): q = the quotient
   // of (p - y) / (x - z) (L - 1 coefficients), *rem = p(z) - y
@@ -1968,9 +1957,8 @@ static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64
   PBF_HIP(hipGetLastError());
   uint64_t pts[9][8];
   {
-    hipEvent_t ready = msm_scalars_ready(ctx, s);
     for (int k = 0; k < 3; ++k)
-      if ((rc = P.commit(C(k), n + 2, k, ready))) return rc;
+      if ((rc = P.commit(C(k), n + 2, k))) return rc;
   }
   P.mark("round 1 commits (3 MSM)");
 
@@ -2088,10 +2076,9 @@ static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64
   // (round 6: the mark now precedes the t_lo commitment, which rounds 4-5 counted here)
   P.mark("round 3 quotient + INTT");
   {
-    hipEvent_t ready = msm_scalars_ready(ctx, s);
-    if ((rc = P.commit(tq, m, 4, ready))) return rc;            // t_lo
-    if ((rc = P.commit(tq + 4 * m, m, 5, ready))) return rc;    // t_mid
-    if ((rc = P.commit(tq + 8 * m, m, 6, ready))) return rc;    // t_hi
+    if ((rc = P.commit(tq, m, 4))) return rc;            // t_lo
+    if ((rc = P.commit(tq + 4 * m, m, 5))) return rc;    // t_mid
+    if ((rc = P.commit(tq + 8 * m, m, 6))) return rc;    // t_hi
   }
   P.mark("round 3 commits (3 MSM)");
 
@@ -2216,9 +2203,8 @@ static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64
   uint64_t* W3 = W0;  // W1 still feeds the W_z commitment's MSM
   if ((rc = P.synth_div(zx, n + 3, zw, zw_z, W3, "W_zw division left a remainder (plonk.rs:442)"))) return rc;
   {
-    hipEvent_t ready = msm_scalars_ready(ctx, s);
-    if ((rc = P.commit(W1, wlen, 7, ready))) return rc;
-    if ((rc = P.commit(W3, n + 2, 8, ready))) return rc;
+    if ((rc = P.commit(W1, wlen, 7))) return rc;
+    if ((rc = P.commit(W3, n + 2, 8))) return rc;
   }
   if ((rc = P.finish_commits(9, pts))) return rc;
   P.mark("round 5 openings + 2 MSM");

@@ -31,13 +31,9 @@ using namespace pbf;
 namespace {
 
 constexpr uint32_t VB_PART = 64;  // column-sum partial blocks per column (one wave in step 2)
-// The E1 MSM runs over W_z, W_zw gathered compactly (2 count points). The A/B build (make
-// vbfull) runs it over all 9 count proof points in place with 7 zero scalars per proof instead.
-#ifdef PBF_VB_E1_FULL
-constexpr uint32_t E1_N = 9, E1_AT = 7;
-#else
+// The E1 MSM runs over W_z, W_zw gathered compactly: E1_N points and scalars per proof, rho and
+// rho u at offset E1_AT.
 constexpr uint32_t E1_N = 2, E1_AT = 0;
-#endif
 
 struct VbParams {
   U256 k1, k2, omega, n_inv;  // Montgomery
@@ -272,9 +268,7 @@ struct Batch {
     PBF_HIP(hipGetLastError());
     uint64_t e1[8], e2[8];
     if ((rc = pbf_msm_g1_bn254_dev(ctx, P, S, 9 * len + 9, e2, s))) return rc;
-    if ((rc = pbf_msm_g1_bn254_dev(ctx, E1_N == 9 ? pts + 72 * lo : e1p + 16 * lo, e1s + 4 * E1_N * lo, E1_N * len, e1,
-                                   s)))
-      return rc;
+    if ((rc = pbf_msm_g1_bn254_dev(ctx, e1p + 16 * lo, e1s + 4 * E1_N * lo, E1_N * len, e1, s))) return rc;
     // e(sum rho E1, [s]G2) e(-sum rho E2, G2) == 1
     uint64_t g1s[16], g2s[32];
     memcpy(g1s, e1, 64);

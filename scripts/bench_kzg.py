@@ -4,13 +4,10 @@ W_z) of len = 2^20 and 2^24 coefficients, then verification at count = 1 / 256 /
 after a warm-up each.
   commit   pbf_kzg_commit_bn254_dev (6 fixed-base MSMs)
   open     pbf_kzg_open_bn254_dev including its MSM
-  sweeps   the opening without its MSM (evaluations, weighted sum, division). Needs the A/B build,
-           whose switch PBF_KZG_NO_MSM is read from the environment per call:
-               make -C plonk-by-fingers_amd/csrc ab && PBF_LIB=plonk-by-fingers_amd/libpbf_ab.so scripts/bench_kzg.py
-           With the product build, which reads no environment, this row is skipped.
   verify   pbf_kzg_verify_bn254
 Prints the median and min-max wall time per row. (profiles/kzg/open_ab.txt is this script's output
-from when it also alternated a fused single-sweep kernel with the sweeps: DESIGN.md 3.9.)
+from when it also timed the opening's sweeps without the MSM and alternated a fused single-sweep
+kernel with them: DESIGN.md 3.9.)
 Usage: bench_kzg.py [log2 len ...]   (default 20 24)"""
 import ctypes
 import os
@@ -27,7 +24,6 @@ from bench_prover import G2  # noqa: E402
 
 R = pbf.BN254_R
 BATCH, REPS, S = 6, 7, 0x5EED0005C0FFEE
-AB = "_ab" in os.path.basename(pbf.LIB_PATH)
 
 
 def timed(fn, reps=REPS):
@@ -68,12 +64,6 @@ def main(logs):
         def opn():
             return ctx.kzg_open_dev(dsrs.data_ptr(), ln, polys.data_ptr(), ln, ln, BATCH, z, weights, stream=sp)
 
-        if AB:
-            os.environ["PBF_KZG_NO_MSM"] = "1"
-            show(f"sweeps 2^{lg} x {BATCH} (no MSM)", timed(opn))
-            os.environ["PBF_KZG_NO_MSM"] = "0"
-        else:
-            print(f"# len = 2^{lg}: sweeps-only row skipped (not the A/B build)")
         show(f"commit 2^{lg} x {BATCH}",
              timed(lambda: ctx.kzg_commit_dev(dsrs.data_ptr(), ln, polys.data_ptr(), ln, ln, BATCH, stream=sp)))
         show(f"open 2^{lg} x {BATCH} (with MSM)", timed(opn))

@@ -82,24 +82,75 @@ def test_single_hip_runtime_in_process():
 
 
 def test_product_library_reads_no_tuning_environment():
-    """the product build never takes a schedule or a code path from the
-    environment -- tuning goes through pbf_ctx_set_option (include/pbf.h) and the A/B switches
-    of measured-negative variants are compiled in only with -DPBF_AB (make ab). The only
-    variable names left in libpbf.so are the RCCL library path and the single-device test hook
-    of the RCCL branch (csrc/group.hip)."""
+    """the library never takes a schedule or a code path from the
+    environment -- tuning goes through pbf_ctx_set_option (include/pbf.h), and there is no build
+    that reads switches of alternative variants from it either. The only variable names in
+    libpbf.so, and the only getenv calls in csrc/, are the RCCL library path and the
+    single-device test hook of the RCCL branch (csrc/group.hip)."""
     import pbf
 
     data = open(pbf.LIB_PATH, "rb").read()
     names = set(re.findall(rb"PBF_[A-Z0-9_]{3,}", data))
     assert names <= {b"PBF_RCCL_LIB", b"PBF_GROUP_FORCE_RCCL"}, sorted(names)
-    src = os.path.join(ROOT, "plonk-by-fingers_amd", "csrc")
     calls = []
+    for fn, text in sorted(csrc_sources().items()):
+        calls += [(fn, m) for m in re.findall(r"getenv\s*\(\s*([^)]*?)\s*\)", text)]
+    assert calls == [("group.hip", '"PBF_RCCL_LIB"'), ("group.hip", '"PBF_GROUP_FORCE_RCCL"')], calls
+
+
+def csrc_sources():
+    """csrc/*.hip and *.hpp by file name, comments blanked out (line structure kept)."""
+    src = os.path.join(ROOT, "plonk-by-fingers_amd", "csrc")
+    blank = lambda m: re.sub(r"[^\n]", " ", m.group(0))
+    out = {}
     for fn in os.listdir(src):
         if fn.endswith((".hip", ".hpp")):
-            calls += [(fn, m) for m in re.findall(r"getenv\((\"?[A-Za-z_]+\"?)\)", open(os.path.join(src, fn)).read())]
-    # group.hip's two names and internal.hpp's ab_env (PBF_AB builds only)
-    assert sorted(calls) == [("group.hip", '"PBF_GROUP_FORCE_RCCL"'), ("group.hip", '"PBF_RCCL_LIB"'),
-                             ("internal.hpp", "name")], calls
+            text = open(os.path.join(src, fn)).read()
+            out[fn] = re.sub(r"//[^\n]*|/\*.*?\*/", blank, text, flags=re.S)
+    return out
+
+
+def kernel_definitions(text):
+    """(name, offset of the name) of every __global__ function declared in `text`: the first
+    identifier after `__global__ void` that is not a launch-bound or attribute clause."""
+    found = []
+    for m in re.finditer(r"\b__global__\b", text):
+        i = m.end()
+        while True:
+            t = re.compile(r"\s*(\w+)").match(text, i)
+            assert t, text[m.start():m.start() + 120]
+            word, i = t.group(1), t.end()
+            if word in ("void", "static", "inline"):
+                continue
+            if word not in ("__launch_bounds__", "__attribute__"):
+                found.append((word, t.start(1)))
+                break
+            depth = 0  # skip the clause's balanced parentheses
+            while True:
+                depth += {"(": 1, ")": -1}.get(text[i], 0)
+                i += 1
+                if depth == 0 and text[i - 1] == ")":
+                    break
+    return found
+
+
+def test_every_kernel_has_a_launch():
+    """A __global__ function that nothing in csrc/ names outside its own declaration (and
+    outside comments) cannot run in the shipped library: it is dead code that still costs build
+    time and review. Kernels are launched by name here (directly or through a function-pointer
+    selection that names them), so a plain search decides it."""
+    sources = csrc_sources()
+    kernels = []
+    for fn, text in sources.items():
+        kernels += [(fn, name, at) for name, at in kernel_definitions(text)]
+    assert len(kernels) > 100, len(kernels)  # the search itself found the kernels
+    declared = {(fn, at) for fn, _, at in kernels}
+    unlaunched = []
+    for fn, name, _ in kernels:
+        uses = [(f, m.start()) for f, text in sources.items() for m in re.finditer(r"\b%s\b" % name, text)]
+        if not [u for u in uses if u not in declared]:
+            unlaunched.append((fn, name))
+    assert not unlaunched, unlaunched
 
 
 def test_set_option_is_declared_with_its_names():

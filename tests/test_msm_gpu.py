@@ -100,10 +100,10 @@ def _dlog_msm(ctx, t_ints, s_ints):
 
 @pytest.mark.parametrize("kind", ["equal", "digit_edges", "sparse", "chunk_sizes"])
 def test_msm_bucket_chunking_and_signed_digits(ctx, kind):
-    """Load-balanced accumulation (csrc/msm.hip msm_chunk_acc / msm_chunk_join) and the
-    signed-digit recoding: buckets spanning many 32-entry chunks, digits at the recoding
-    boundaries (0x7fff, 0x8000, 0x8001, 0xffff carry chains), mostly-zero windows, and sizes
-    around the chunk length."""
+    """Load-balanced accumulation (csrc/msm.hip msm_chunk_acc_l29r / msm_l29_finish, joined by
+    msm_join_step / msm_join_rest) and the signed-digit recoding: buckets spanning many
+    43-entry chunks, digits at the recoding boundaries (0x7fff, 0x8000, 0x8001, 0xffff carry
+    chains), mostly-zero windows, and sizes around the chunk length."""
     rnd = random.Random(hash(kind) & 0xFFFF)
     if kind == "equal":  # one bucket per window holding all n points (spans n/32 chunks)
         n = 5000
