@@ -374,3 +374,183 @@ def test_fixed_base_heavy_buckets(ctx, c):
     ctx.set_option("msm.fx_c", None)
 
 
+# ---- the exceptional exits of the group law through the real MSM kernels --------------------------
+# Every addition of csrc/ec_bn254.hpp and csrc/msm_l29.hpp has four exits (an identity operand,
+# P + P, P + (-P), the generic formula; tests/test_group_device_gpu.py enters each directly). Random
+# points meet only the last one, so the tests below make the accumulation, the join kernels, the
+# C / D and subset trees and the quad kernels add equal and opposite points: P_i = t_i G with few
+# distinct t_i, the result pinned by the discrete logs, (sum s_i t_i mod r) G by one oracle
+# product, (0, 0) when the sum is 0.
+_FORMS = ("windowed", "fx16", "fx18", "fx20", "fx22", "range")
+_RANGE_FIRST = 5
+
+
+def _msm_const(name):
+    """A constexpr of csrc/msm.hip (the join regimes' bounds)."""
+    import os
+    import re
+
+    src = open(os.path.join(os.path.dirname(os.path.abspath(pbf.__file__)), "..", "csrc", "msm.hip")).read()
+    return int(re.search(r"constexpr uint32_t %s = (\d+);" % name, src).group(1))
+
+
+def _rows(values, idx):
+    """The (n, 4) limb rows values[idx[i]] (few distinct values, any n)."""
+    table = np.asarray(pbf.ints_to_limbs(values), dtype=np.uint64).reshape(len(values), 4)
+    return table[np.asarray(idx)]
+
+
+def _msm_form(ctx, form, t_rows, s_rows):
+    """sum s_i (t_i G) through one form of the MSM: the windowed msm_g1_dev, the fixed-base
+    msm_g1_fixed_dev at one window width, or msm_g1_fixed_range_dev with first > 0."""
+    import torch
+
+    n = len(t_rows)
+    first = _RANGE_FIRST if form == "range" else 0
+    if first:  # points before the range: never read
+        t_rows = np.concatenate([_rows([7], [0] * first), t_rows])
+    dt = torch.from_numpy(np.ascontiguousarray(t_rows).reshape(-1).view(np.int64)).cuda()
+    ds = torch.from_numpy(np.ascontiguousarray(s_rows).reshape(-1).view(np.int64)).cuda()
+    dp = torch.empty((n + first) * 8, dtype=torch.int64, device="cuda")
+    st = torch.cuda.current_stream().cuda_stream
+    ctx.g1_mul_base_dev(dt.data_ptr(), dp.data_ptr(), n + first, stream=st)
+    torch.cuda.synchronize()
+    if form == "windowed":
+        return ctx.msm_g1_dev(dp.data_ptr(), ds.data_ptr(), n, stream=st)
+    try:
+        if form == "range":
+            return ctx.msm_g1_fixed_range_dev(dp.data_ptr(), n + first, first, ds.data_ptr(), n)
+        ctx.set_option("msm.fx_c", int(form[2:]))
+        return ctx.msm_g1_fixed_dev(dp.data_ptr(), n, ds.data_ptr(), n)
+    finally:
+        ctx.release_caches()
+        ctx.set_option("msm.fx_c", None)
+
+
+_G_MUL = {}
+
+
+def _g_mul(z):
+    z %= R
+    if z not in _G_MUL:
+        _G_MUL[z] = enc(bn254.g1_mul(bn254.G1_GEN, z) if z else None)
+    return _G_MUL[z]
+
+
+_ONE_K = 0x1F3D5B79A4C6E8021357
+_ONE_S = random.Random(0x0E5).randrange(1 << 252, R)  # full width: every window has a digit
+_ONE_POINT = [(n, f) for n in (100, 255, 256, 5000, 1 << 16) for f in _FORMS] + [(1 << 18, "fx16"), (1 << 18, "fx22")]
+
+
+@pytest.mark.parametrize("n,form", _ONE_POINT)
+def test_msm_one_point_every_join_is_a_doubling(ctx, n, form):
+    """n copies of one point under one full-width scalar: every bucket's run starts with P + P,
+    every chunk partial of a bucket is 43 copies of one table point, so every addition of every
+    join is a doubling of two different representations. The single bucket per window spans
+    n / 43 chunks: about 2 (msm_fx_resolve's sequential sum), 116 (msm_join_heavy; the windowed
+    form's msm_join_step and msm_join_rest), 1524 (past HJ_MAX: msm_join_chunks) and 6096 (past
+    FX_JOIN_GROUP_C: msm_join_rest_g); n = 255 and 256 are the two sorts."""
+    ch = _msm_const("MSM_CH")
+    seq, hj, grp, grp_c = (_msm_const(k) for k in ("FX_SEQ_CAP", "HJ_MAX", "FX_JOIN_GROUP", "FX_JOIN_GROUP_C"))
+    span = (n - 1) // ch
+    assert {100: 0 < span <= seq, 255: seq < span <= grp, 256: seq < span <= grp, 5000: grp < span <= hj,
+            1 << 16: hj < span <= grp_c, 1 << 18: span > grp_c}[n], (n, span)
+    got = _msm_form(ctx, form, _rows([_ONE_K], [0] * n), _rows([_ONE_S], [0] * n))
+    assert got == _g_mul(n * _ONE_S * _ONE_K)
+
+
+_CANCEL = [(n, blk, f) for n, blk in ((100, 1), (100, 50), (5000, 1), (5000, 2500), (1 << 16, 64), (1 << 16, 1 << 15))
+           for f in _FORMS]
+
+
+@pytest.mark.parametrize("n,block,form", _CANCEL)
+def test_msm_cancellation_is_the_identity(ctx, n, block, form):
+    """Half the points k G and half -k G (alternating in blocks of `block`) under one scalar: every
+    bucket sum and the result are the identity. P + (-P) in the accumulation (block = 1: every
+    other step) and in the joins, identity partials through store_raw / raw_to_xyzz, all-identity
+    trees, and (0, 0) as the encoding of a non-empty MSM."""
+    idx = (np.arange(n) // block) % 2
+    assert 2 * int(idx.sum()) == n
+    got = _msm_form(ctx, form, _rows([_ONE_K, R - _ONE_K], idx), _rows([_ONE_S], [0] * n))
+    assert got == (0, 0)
+
+
+def _signed_digits(s, c, nw):
+    """The signed-digit recoding of csrc/msm.hip (msm_digits, fx_digit): c-bit windows, a digit
+    above 2^(c-1) becomes d - 2^c with a carry of 1 into the next window."""
+    out, carry = [], 0
+    for w in range(nw):
+        d = ((s >> (c * w)) & ((1 << c) - 1)) + carry
+        carry = 1 if d > (1 << (c - 1)) else 0
+        out.append(d - (1 << c) if carry else d)
+    assert carry == 0
+    return out
+
+
+def _bucket_log_sums(t, s, c, fixed):
+    """{bucket set: {bucket: sum of the discrete logs of its entries mod r}}: one set per window
+    (windowed form: bucket |d| - 1 of window w holds +-P_i) or one in all (fixed-base form: bucket
+    |d| - 1 holds +-2^(c w) P_i, the table's entry)."""
+    sets = {}
+    for ti, si in zip(t, s):
+        for w, d in enumerate(_signed_digits(si, c, 16 if not fixed else (255 + c - 1) // c)):
+            if d:
+                b = sets.setdefault(0 if fixed else w, {})
+                weight = pow(2, c * w, R) if fixed else 1
+                b[abs(d) - 1] = (b.get(abs(d) - 1, 0) + (1 if d > 0 else -1) * weight * ti) % R
+    return sets
+
+
+# bucket -> the small logs of its entries (each list is repeated _COLL_REP times in the bucket).
+# Buckets b and b + 1 inside an aligned group of 4 are added in sequence by the C sums (c = 16: one
+# quad per group, msm_fxg_cd_q; the windowed and wide forms: one lane per 8, msm_fx_cd_seq /
+# msm_fxg_cd_seq); buckets b and b + 16 meet in the quad trees of the subset sums
+# (msm_fx_subsets_q / msm_fxg_subsets_q: D_l and D_(l+16) are tree partners 8 quads apart).
+_COLL = {0: [3, 2], 1: [1, 1, 3], 2: [-3, -2], 3: [2, -2, 1, -1],   # 5, 5, -5, 0
+         4: [3, 3, 1], 6: [2, 2, 3], 7: [-3, -3, -1],               # 7, empty, 7, -7
+         8: [1], 9: [2, -1], 10: [3, -2], 11: [1],                  # 1, 1, 1, 1
+         12: [-2, -2], 13: [-3, -1], 15: [3, 1],                    # -4, -4, empty, 4
+         16: [1, 1, 1, 2], 17: [-3, -2], 18: [-1, -1, -3], 19: [3, -3],    # = b0, -b1, = b2, 0 and 0
+         20: [2, 2, 2, 1], 21: [1], 22: [-3, -3, -1], 23: [-2, -2, -3],    # = b4, (b5 empty), -b6, = b7
+         25: [3, -2], 26: [-1], 27: [2, -1],                               # (b8 alone), = b9, -b10, = b11
+         28: [-3, -1], 29: [2, 2], 31: [2, 2]}                             # = b12, -b13, both empty, = b15
+_COLL_REP = 20
+_COLL_WINDOWS = (0, 1, 5)
+
+
+@pytest.mark.parametrize("form", _FORMS)
+def test_msm_colliding_bucket_sums(ctx, form):
+    """t_i in {+-1, +-2, +-3} and s_i = d 2^(c w) for d <= 32 and three windows w, the entries
+    chosen so that neighbouring buckets hold equal sums (of different points: different XYZZ
+    representations of one point), opposite sums, zero sums and nothing: the C / D trees, the
+    subset trees and fx_tree_q (single-lane and quad) take their doubling and identity exits.
+    The bucket sums are computed from a restatement of the signed-digit recoding and the
+    collisions asserted before the GPU is called."""
+    c = int(form[2:]) if form.startswith("fx") else 16
+    t, s = [], []
+    for w in _COLL_WINDOWS:
+        for b, logs in _COLL.items():
+            for _ in range(_COLL_REP):
+                t += [x % R for x in logs]
+                s += [(b + 1) << (c * w)] * len(logs)
+    order = list(range(len(t)))
+    random.Random(0xC011).shuffle(order)
+    t, s = [t[i] for i in order], [s[i] for i in order]
+    assert 2000 <= len(t) <= 5000
+    sets = _bucket_log_sums(t, s, c, form != "windowed")
+    assert sorted(sets) == ([0] if form != "windowed" else sorted(_COLL_WINDOWS))
+    for sums in sets.values():
+        pairs = [(b, b + 1) for b in range(31) if b % 4 != 3 and b in sums and b + 1 in sums]
+        equal = [p for p in pairs if sums[p[0]] and sums[p[0]] == sums[p[1]]]
+        opposite = [p for p in pairs if sums[p[0]] and (sums[p[0]] + sums[p[1]]) % R == 0]
+        empty = [b for b in range(1, 31) if b not in sums and b - 1 in sums and b + 1 in sums]
+        zero = [b for b in sums if sums[b] == 0]
+        assert len(equal) >= 3 and len(opposite) >= 2 and len(empty) >= 2 and len(zero) >= 1, (equal, opposite, empty, zero)
+        far = [(b, b + 16) for b in range(16) if sums.get(b) and sums.get(b + 16)]  # tree partners
+        far_equal = [p for p in far if sums[p[0]] == sums[p[1]]]
+        far_opposite = [p for p in far if (sums[p[0]] + sums[p[1]]) % R == 0]
+        assert len(far_equal) >= 3 and len(far_opposite) >= 2, (far_equal, far_opposite)
+    idx_t = {v: i for i, v in enumerate(sorted(set(t)))}
+    idx_s = {v: i for i, v in enumerate(sorted(set(s)))}
+    got = _msm_form(ctx, form, _rows(sorted(idx_t), [idx_t[v] for v in t]), _rows(sorted(idx_s), [idx_s[v] for v in s]))
+    assert got == _g_mul(sum(a * b for a, b in zip(s, t)))
