@@ -91,6 +91,7 @@ constexpr size_t COSET_SHIFTS_PER_PLAN = 4;
 struct NttPlan {
   uint64_t m = 0, omega = 0, n = 0;
   int inverse = 0;
+  uint64_t root = 0;       // the transform's own root: omega, or omega^-1 for the inverse
   FieldKind kind = FIELD_GOLDILOCKS;
   FieldArgs fa{};
   uint32_t log_n = 0;
@@ -99,11 +100,11 @@ struct NttPlan {
   std::vector<int> logr;   // radix per pass (empty => small kernel)
   int e64 = -1;            // w_64 = 2^e64 for a standard Goldilocks root, else -1
   std::vector<std::shared_ptr<DevBuf>> twpass;  // per-pass [r][k] twiddles (empty buffer => two-level)
-  int w = 16;              // columns per workgroup
   uint32_t tw_bits = 0;
   DevBuf tw0, tw1, small_tw;
-  std::vector<std::shared_ptr<DevBuf>> rtab;  // per pass
+  int twmax_log = 24;      // option ntt.twmax_log: no single-level table above 2^twmax_log entries
   bool gl = false;         // passes run on ntt_gl_pass_kernel (standard Goldilocks roots)
+  std::vector<std::shared_ptr<DevBuf>> rtab;  // per pass of ntt_pass_kernel (!gl): w_R^m, m < R
   std::vector<std::shared_ptr<DevBuf>> tc;    // per pass: stage-C tables of ntt_gl_pass_kernel
   // last pass without a full [r][k] table: w^(r k) = B[kb][r] * A[r][w] for k = kb*W + w
   // (A: R x W, B: Ns/W x R; null when unused), W = tws_w columns per tile

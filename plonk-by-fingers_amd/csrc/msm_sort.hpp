@@ -21,15 +21,12 @@
 
 namespace pbf {
 
-#ifndef PBF_RS_ITEMS
-#define PBF_RS_ITEMS 32
-#endif
 // RS_ITEMS entries per thread (a tile of 8192 entries: 64 KiB of LDS for the locally sorted
 // copy, two workgroups per CU; runs of ~32 entries per digit and tile on the store side; 2^28
 // pairs: 5.1 ms with 4096-entry tiles, 4.0 ms with 8192, scripts/ubench/sort_bench.hip).
 // RS_TILE: the smallest tile any caller may pick (it sizes the histogram scratch); RS_TILE_MAX
 // the largest (it bounds m).
-constexpr int RS_T = 256, RS_ITEMS = PBF_RS_ITEMS, RS_TILE = RS_T * 16, RS_TILE_MAX = RS_T * 64;
+constexpr int RS_T = 256, RS_ITEMS = 32, RS_TILE = RS_T * 16, RS_TILE_MAX = RS_T * 64;
 
 // Signed digit code of C = uint16_t (windows of up to 16 bits) or uint32_t (wider fixed-base
 // windows): |d| - 1 for d > 0, the top bit | (|d| - 1) for d < 0, all ones (rs_none<C>) for

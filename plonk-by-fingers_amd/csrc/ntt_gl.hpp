@@ -29,23 +29,6 @@
 #pragma once
 #include "ntt_kernels.hpp"
 
-// Timing experiment only (make nomath): -DPBF_GL_NOMATH drops every twiddle multiply and
-// register DFT of ntt_gl_pass_kernel, leaving its loads, LDS exchanges, barriers and
-// stores: the data-movement floor of the kernel. Never the product build.
-#ifdef PBF_GL_NOMATH
-#define PBF_GL_MATH(x) do { } while (0)
-#else
-#define PBF_GL_MATH(x) x
-#endif
-// Timing experiment only (make nomem): every tile loads tile 0 of polynomial 0 (L2-resident)
-// and stores only values equal to a sentinel that never occurs: the kernel's compute, LDS
-// and barrier time without HBM traffic.
-#ifdef PBF_GL_NOMEM
-#define PBF_GL_NOMEM_ON 1
-#else
-#define PBF_GL_NOMEM_ON 0
-#endif
-
 namespace pbf {
 
 struct GlPassArgs {
@@ -185,12 +168,8 @@ struct GlShape {
   // Y rows r2: padded by W (YP = 65 W) so that the four r2 rows of one stage-B write
   // instruction fall on both halves of the banks; for W = 16 the same spread comes from
   // XOR-ing k1's low bit with r2's (YX: no padding, a 4096-element tile is exactly 32 KiB and
-  // five workgroups fit a CU; PBF_GL_PAD_Y builds the padded layout for A/B)
-#ifdef PBF_GL_PAD_Y
-  static constexpr bool YX = false;
-#else
+  // five workgroups fit a CU)
   static constexpr bool YX = W == 16 && C > 1;
-#endif
   static constexpr int YP = (YX ? 64 : 65) * W;     // Y row pitch (elements)
   static constexpr int LDS = (C * YP > TILE) ? C * YP : TILE;
   static constexpr bool LDS32K = LDS * 8 <= 32768;  // five workgroups per CU by LDS
@@ -262,7 +241,6 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
   using G = Goldilocks;
   uint32_t poly, kb;
   gl_tile_coords(a, tile, tiles, &poly, &kb);
-  if constexpr (PBF_GL_NOMEM_ON) kb &= 1, poly = 0;
   const uint64_t j0 = (uint64_t)kb * W;
   const uint64_t* in = a.in + (uint64_t)poly * a.in_pitch;
   const uint64_t stride = a.n >> LOGR;  // input rows (r) are n/R long
@@ -339,15 +317,11 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
         }
       }
 #pragma unroll
-      for (int m = 0; m < 8; ++m) PBF_GL_MATH(v[8 * h + m] = G::mul(v[8 * h + m], tw[m], f));
-#ifdef PBF_GL_NOMATH
-#pragma unroll
-      for (int m = 0; m < 8; ++m) v[8 * h + m] ^= tw[m];
-#endif
+      for (int m = 0; m < 8; ++m) v[8 * h + m] = G::mul(v[8 * h + m], tw[m], f);
     }
   }
 #pragma unroll
-  for (int u = 0; u < 4; ++u) PBF_GL_MATH((dft_reg<G, 2, sub_root_exp(E64, 2)>(v + u * 4, nullptr, f)));
+  for (int u = 0; u < 4; ++u) dft_reg<G, 2, sub_root_exp(E64, 2)>(v + u * 4, nullptr, f);
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const int idx = t + NT * u;  // = s2*(C*W) + (r2*W + w)
@@ -364,7 +338,6 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
     const int rw = (wave % Sh::WPQ) * 64 + (t & 63);  // r2*W + w
 #pragma unroll
     for (int s2 = 0; s2 < 16; ++s2) v[s2] = lds[(q1 * 16 + s2) * (C * W) + rw];
-#ifndef PBF_GL_NOMATH
     if constexpr (RG == 3) {
       uint64_t p = t3[0];
       const uint64_t d = t3[1];
@@ -385,7 +358,6 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
       }
       dft_reg_tail<G, 4, sub_root_exp(E64, 4), GL_B_LEVELS>(v, f);
     }
-#endif
     __syncthreads();
     const int r2 = rw / W, w = rw % W;
 #pragma unroll
@@ -451,24 +423,19 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
     }
     if (scaled) {
 #pragma unroll
-      for (int m = 0; m < Sh::NSUB_C * C; ++m) PBF_GL_MATH(x[m] = G::mul(x[m], tw[m], f));
+      for (int m = 0; m < Sh::NSUB_C * C; ++m) x[m] = G::mul(x[m], tw[m], f);
     } else {
       // r2 = 0 rows multiply by 1 and are skipped; k1 = 0 lanes multiply by 1 (a per-lane
       // branch would only diverge)
 #pragma unroll
       for (int u = 0; u < Sh::NSUB_C; ++u)
 #pragma unroll
-        for (int r2 = 1; r2 < C; ++r2) {
-          PBF_GL_MATH(x[u * C + r2] = G::mul(x[u * C + r2], tw[u * C + r2], f));
-#ifdef PBF_GL_NOMATH
-          x[u * C + r2] ^= tw[u * C + r2];
-#endif
-        }
+        for (int r2 = 1; r2 < C; ++r2) x[u * C + r2] = G::mul(x[u * C + r2], tw[u * C + r2], f);
     }
   }
   if constexpr (C > 1) {
 #pragma unroll
-    for (int u = 0; u < Sh::NSUB_C; ++u) PBF_GL_MATH((dft_reg<G, LOGC, sub_root_exp(E64, LOGC)>(x + u * C, nullptr, f)));
+    for (int u = 0; u < Sh::NSUB_C; ++u) dft_reg<G, LOGC, sub_root_exp(E64, LOGC)>(x + u * C, nullptr, f);
   }
 
   // ---------------- store
@@ -487,9 +454,7 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
         for (int k2 = 0; k2 < C; ++k2) x[u * C + bitrev_c(k2, LOGC)] = G::mul(x[u * C + bitrev_c(k2, LOGC)], tw[k2], f);
       }
 #pragma unroll
-      for (int k2 = 0; k2 < C; ++k2)
-        if (!PBF_GL_NOMEM_ON || x[u * C + bitrev_c(k2, LOGC)] == 0x123456789ull)
-          o[base + k1 + 64 * k2] = x[u * C + bitrev_c(k2, LOGC)];
+      for (int k2 = 0; k2 < C; ++k2) o[base + k1 + 64 * k2] = x[u * C + bitrev_c(k2, LOGC)];
     }
   } else {
     const uint32_t lns = SP == 2 ? (uint32_t)LOGR : a.log_ns;
@@ -511,9 +476,7 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
           for (int k2 = 0; k2 < C; ++k2) x[u * C + bitrev_c(k2, LOGC)] = G::mul(x[u * C + bitrev_c(k2, LOGC)], tw[k2], f);
         }
 #pragma unroll
-        for (int k2 = 0; k2 < C; ++k2)
-          if (!PBF_GL_NOMEM_ON || x[u * C + bitrev_c(k2, LOGC)] == 0x123456789ull)
-            out[base + ((uint64_t)(k1 + 64 * k2) << lns)] = x[u * C + bitrev_c(k2, LOGC)];
+        for (int k2 = 0; k2 < C; ++k2) out[base + ((uint64_t)(k1 + 64 * k2) << lns)] = x[u * C + bitrev_c(k2, LOGC)];
       } else {
         const uint64_t smask = (1ull << sl) - 1;
 #pragma unroll

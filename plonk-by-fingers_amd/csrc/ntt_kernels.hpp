@@ -16,21 +16,12 @@
 
 namespace pbf {
 
-// Timing-only modes (PassArgs::dbg) are compiled in only with -DPBF_NTT_TIMING_MODES:
-// the per-element runtime checks they need split the kernels into many basic blocks.
-#ifdef PBF_NTT_TIMING_MODES
-#define PBF_DBG(a, bit) (((a).dbg & (bit)) != 0)
-#else
-#define PBF_DBG(a, bit) false
-#endif
-
 struct PassArgs {
   const uint64_t* in;    // pass input  (batch * n elements)
   uint64_t* out;         // pass output (batch * n elements)
   const uint64_t* tw0;   // w^m for m < 2^tw_bits            (two-level table, low part)
   const uint64_t* tw1;   // w^(m << tw_bits) for m < n>>tw_bits (high part)
   const uint64_t* rtab;  // w_R^m = w^(m*n/R) for m < R
-  const uint64_t* twfull; // unused (always null; kept for the argument layout)
   const uint64_t* twpass; // this pass's twiddles T[r][k] = w^((n/(Ns*R))*r*k), or null
   uint64_t n;            // transform size
   uint64_t n_inv;        // n^-1, applied to outputs when scale != 0
@@ -39,7 +30,6 @@ struct PassArgs {
   uint32_t tw_bits;
   uint32_t blocks_per_poly;
   uint32_t scale;
-  uint32_t dbg;            // timing builds only (PBF_NTT_TIMING_MODES): 1 = no HBM traffic, 2 = no butterflies
   uint32_t cur_poly;       // set per tile inside the kernel
   uint32_t out_split_log;  // != 0: last pass stores destination-major [n/S][batch][S], S = 2^out_split_log
   uint32_t batch;
@@ -48,15 +38,16 @@ struct PassArgs {
 };
 
 // ---- compile-time helpers ----------------------------------------------------
-// In-workgroup stages: radix 2^LQ (LQ = log2 of the largest register radix), the
-// remainder radix first.
-__host__ __device__ constexpr int ntt_nstages(int logr, int lq) { return (logr + lq - 1) / lq; }
-__host__ __device__ constexpr int ntt_stage_logq(int logr, int s, int lq) {
-  return (logr % lq == 0) ? lq : (s == 0 ? logr % lq : lq);
+// In-workgroup stages: radix 2^NTT_LQ (log2 of the largest register radix: 16-point register
+// sub-DFTs), the remainder radix first.
+constexpr int NTT_LQ = 4;
+__host__ __device__ constexpr int ntt_nstages(int logr) { return (logr + NTT_LQ - 1) / NTT_LQ; }
+__host__ __device__ constexpr int ntt_stage_logq(int logr, int s) {
+  return (logr % NTT_LQ == 0) ? NTT_LQ : (s == 0 ? logr % NTT_LQ : NTT_LQ);
 }
-__host__ __device__ constexpr int ntt_stage_logl(int logr, int s, int lq) {
+__host__ __device__ constexpr int ntt_stage_logl(int logr, int s) {
   int l = 0;
-  for (int i = 0; i < s; ++i) l += ntt_stage_logq(logr, i, lq);
+  for (int i = 0; i < s; ++i) l += ntt_stage_logq(logr, i);
   return l;
 }
 __host__ __device__ constexpr int bitrev_c(int x, int bits) {
@@ -213,26 +204,12 @@ __host__ __device__ constexpr int sub_root_exp(int e64, int logq) {
   return e64 < 0 ? -1 : (e64 * (64 >> logq)) % 192;
 }
 
-// Workgroup barrier of the in-tile stages. DB (LDS-DMA double-buffered) kernels use a
-// raw s_barrier with lgkmcnt(0) only, so the next tile's LDS-DMA stays in flight
-// (hipcc's __syncthreads() would emit vmcnt(0) and drain it: guide "Pipelining
-// across barriers").
-template <bool DB>
-__device__ __forceinline__ void tile_barrier() {
-  if constexpr (DB) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  } else {
-    __syncthreads();
-  }
-}
-
 // Raw stage-0 inputs of one tile into registers (the same thread -> element map as stage 0).
-template <int LOGR, int W, int NT, int LQ>
+template <int LOGR, int W, int NT>
 __device__ __forceinline__ void tile_load(uint64_t* v, const PassArgs& a, const uint64_t* in, uint64_t j0, int t) {
   constexpr int R = 1 << LOGR;
   constexpr int PER = (R * W) / NT;
-  constexpr int Q = 1 << ntt_stage_logq(LOGR, 0, LQ);
+  constexpr int Q = 1 << ntt_stage_logq(LOGR, 0);
 #pragma unroll
   for (int u = 0; u < PER / Q; ++u) {
     const int sub = t + NT * u;
@@ -240,8 +217,7 @@ __device__ __forceinline__ void tile_load(uint64_t* v, const PassArgs& a, const 
 #pragma unroll
     for (int c = 0; c < Q; ++c) {
       const int r = i + c * (R / Q);
-      v[u * Q + c] = PBF_DBG(a, 1) ? (uint64_t)(t * 0x9E3779B9u + r) * 0x100000001ull
-                                 : in[(j0 + w) + (uint64_t)r * (a.n >> LOGR)];
+      v[u * Q + c] = in[(j0 + w) + (uint64_t)r * (a.n >> LOGR)];
     }
   }
 }
@@ -250,15 +226,15 @@ __device__ __forceinline__ void tile_load(uint64_t* v, const PassArgs& a, const 
 // Stage 0 takes the raw tile (registers v) and applies the pass twiddle; later stages read
 // the exchange buffer and apply the stage twiddle from `rt`. (The LDS-DMA double-buffered and
 // register-prefetching persistent forms of rounds 1-2 measured slower; removed in round 6.)
-template <class F, int LOGR, int W, int NT, int LQ, int E64, int S>
+template <class F, int LOGR, int W, int NT, int E64, int S>
 __device__ __forceinline__ void ntt_stage(uint64_t* v, uint64_t* buf, const uint64_t* rt, const uint64_t* wq,
                                           const PassArgs& a, uint64_t* out, uint64_t j0, int t) {
   constexpr int R = 1 << LOGR;
   constexpr int PER = (R * W) / NT;
-  constexpr int NST = ntt_nstages(LOGR, LQ);
-  constexpr int LOGQ = ntt_stage_logq(LOGR, S, LQ);
+  constexpr int NST = ntt_nstages(LOGR);
+  constexpr int LOGQ = ntt_stage_logq(LOGR, S);
   constexpr int Q = 1 << LOGQ;
-  constexpr int L = 1 << ntt_stage_logl(LOGR, S, LQ);
+  constexpr int L = 1 << ntt_stage_logl(LOGR, S);
   constexpr int NSUB = PER / Q;
   constexpr bool LAST = (S == NST - 1);
   const uint64_t n = a.n;
@@ -311,7 +287,7 @@ __device__ __forceinline__ void ntt_stage(uint64_t* v, uint64_t* buf, const uint
     }
   }
   // ---- radix-Q DFTs in registers (wq[m] = w_QMAX^m; w_Q = w_QMAX^(QMAX/Q))
-  constexpr int QMAX = 1 << LQ;
+  constexpr int QMAX = 1 << NTT_LQ;
 #pragma unroll
   for (int u = 0; u < NSUB; ++u) {
     uint64_t wloc[Q / 2 > 0 ? Q / 2 : 1];
@@ -319,9 +295,9 @@ __device__ __forceinline__ void ntt_stage(uint64_t* v, uint64_t* buf, const uint
 #pragma unroll
       for (int m = 0; m < Q / 2; ++m) wloc[m] = wq[m * (QMAX / Q)];
     }
-    if (!PBF_DBG(a, 2)) dft_reg<F, LOGQ, sub_root_exp(E64, LOGQ)>(v + u * Q, wloc, a.f);
+    dft_reg<F, LOGQ, sub_root_exp(E64, LOGQ)>(v + u * Q, wloc, a.f);
   }
-  if constexpr (S > 0) tile_barrier<false>();  // all reads of the exchange buffer are done
+  if constexpr (S > 0) __syncthreads();  // all reads of the exchange buffer are done
   // ---- scatter outputs (uniform output-mode branches hoisted out of the unrolled loops)
   if constexpr (!LAST) {
 #pragma unroll
@@ -358,15 +334,7 @@ __device__ __forceinline__ void ntt_stage(uint64_t* v, uint64_t* buf, const uint
         return ((j >> a.log_ns) << (a.log_ns + LOGR)) + (j & ns_mask) +
                ((uint64_t)((i / L) * L * Q + (i % L) + d * L) << a.log_ns);
       };
-      if (PBF_DBG(a, 1)) {
-#pragma unroll
-        for (int u = 0; u < NSUB; ++u)
-#pragma unroll
-          for (int d = 0; d < Q; ++d) {
-            const uint64_t y = v[u * Q + bitrev_c(d, LOGQ)];
-            if (y == 0x123456789ull) out[kk_of(u, d)] = y;  // keeps the arithmetic live
-          }
-      } else if (sl == 0) {
+      if (sl == 0) {
 #pragma unroll
         for (int u = 0; u < NSUB; ++u)
 #pragma unroll
@@ -385,29 +353,27 @@ __device__ __forceinline__ void ntt_stage(uint64_t* v, uint64_t* buf, const uint
     }
   }
   if constexpr (!LAST) {
-    tile_barrier<false>();
-    ntt_stage<F, LOGR, W, NT, LQ, E64, S + 1>(v, buf, rt, wq, a, out, j0, t);
+    __syncthreads();
+    ntt_stage<F, LOGR, W, NT, E64, S + 1>(v, buf, rt, wq, a, out, j0, t);
   }
 }
 
 // Store the first pass's transposed [w][r] image: outputs y[j0*R .. (j0+W)*R) are contiguous.
-template <int LOGR, int W, int NT, bool DB>
-__device__ __forceinline__ void store_transposed(const uint64_t* buf, uint64_t* out, uint64_t j0, int t,
-                                                 const PassArgs& a) {
+template <int LOGR, int W, int NT>
+__device__ __forceinline__ void store_transposed(const uint64_t* buf, uint64_t* out, uint64_t j0, int t) {
   constexpr int R = 1 << LOGR;
   constexpr int PER = (R * W) / NT;
-  tile_barrier<DB>();
+  __syncthreads();
   uint64_t* o = out + j0 * R;
 #pragma unroll
   for (int u = 0; u < PER; ++u) {
     const int m = t + NT * u;
-    const uint64_t y = buf[(m / R) * (R + 1) + (m % R)];
-    if (!PBF_DBG(a, 1) || y == 0x123456789ull) o[m] = y;
+    o[m] = buf[(m / R) * (R + 1) + (m % R)];
   }
 }
 
 // One Stockham pass over HBM, one tile per workgroup (tiles too large to double-buffer).
-// NT threads, W columns of R = 2^LOGR points, register sub-DFTs of radix up to 2^LQ;
+// NT threads, W columns of R = 2^LOGR points, register sub-DFTs of radix up to 2^NTT_LQ;
 // E64 >= 0 selects shift twiddles for a standard Goldilocks root (w_64 = 2^E64).
 // Waves per SIMD the pass kernels are register-budgeted for: as many as the LDS tile
 // lets reside (R*W*8 bytes per workgroup of NT threads, 160 KiB per CU), at most 8.
@@ -418,14 +384,14 @@ __host__ __device__ constexpr int ntt_waves_per_eu(int e, int nt) {
   return w < 1 ? 1 : (w > 8 ? 8 : w);
 }
 
-template <class F, int LOGR, int W, int NT, int LQ, int E64>
+template <class F, int LOGR, int W, int NT, int E64>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(ntt_waves_per_eu(W << LOGR, NT))))
 ntt_pass_kernel(PassArgs a) {
   constexpr int R = 1 << LOGR;
   constexpr int E = R * W;
   constexpr int PER = E / NT;
-  constexpr int QMAX = 1 << LQ;
-  static_assert(LOGR >= LQ, "register sub-DFTs need R >= 2^LQ");
+  constexpr int QMAX = 1 << NTT_LQ;
+  static_assert(LOGR >= NTT_LQ, "register sub-DFTs need R >= 2^NTT_LQ");
   static_assert(PER >= QMAX && PER % QMAX == 0, "each thread must own whole register sub-DFTs");
   static_assert(E <= 16384, "LDS budget: 128 KiB of elements per workgroup");
   // +W pad keeps the transposed [w][r] image of the first pass bank-conflict free
@@ -457,9 +423,9 @@ ntt_pass_kernel(PassArgs a) {
     for (int m = 0; m < QMAX / 2; ++m) wq[m] = a.rtab[m * (R / QMAX)];
   }
   uint64_t v[PER];
-  tile_load<LOGR, W, NT, LQ>(v, a, in, j0, t);
-  ntt_stage<F, LOGR, W, NT, LQ, E64, 0>(v, lds, a.rtab, wq, b, out, j0, t);
-  if (a.log_ns == 0) store_transposed<LOGR, W, NT, false>(lds, out, j0, t, a);
+  tile_load<LOGR, W, NT>(v, a, in, j0, t);
+  ntt_stage<F, LOGR, W, NT, E64, 0>(v, lds, a.rtab, wq, b, out, j0, t);
+  if (a.log_ns == 0) store_transposed<LOGR, W, NT>(lds, out, j0, t);
 }
 
 // Whole transform of a small n (<= 4096) inside one workgroup per polynomial:

@@ -58,6 +58,55 @@ static int upload(DevBuf& b, const std::vector<uint64_t>& v) {
   return 0;
 }
 
+// ---------------------------------------------------------------- host twiddle tables
+// Every table of this file is built here, on the host, as plain words; the caller uploads it.
+typedef std::vector<uint64_t> Table;
+
+// c s^i, i < count
+static Table geometric(uint64_t c, uint64_t s, uint64_t count, uint64_t m) {
+  Table t(count);
+  uint64_t x = c % m;
+  for (uint64_t i = 0; i < count; ++i) { t[i] = x; x = hmul(x, s, m); }
+  return t;
+}
+
+// Two-level table of c root^i, i < len: first[i] = c root^i (i < 2^bits), second[i] = root^(i << bits),
+// so that c root^i = first[i mod 2^bits] * second[i >> bits]
+static std::pair<Table, Table> two_level_tabs(uint64_t root, uint64_t len, uint32_t bits, uint64_t c, uint64_t m) {
+  return {geometric(c, root, 1ull << bits, m),
+          geometric(1, hpow(root, 1ull << bits, m), ((len - 1) >> bits) + 1, m)};
+}
+
+// Stage-C table of ntt_gl_pass_kernel: tc[r2][k1] = scale * w_R^(r2 k1), r2 < C = R/64, k1 < 64
+static Table stage_c_tab(uint64_t w_r, uint64_t C, uint64_t scale, uint64_t m) {
+  Table tc(C * 64);
+  for (uint64_t r2 = 0; r2 < C; ++r2)
+    for (uint64_t k1 = 0; k1 < 64; ++k1) tc[r2 * 64 + k1] = hmul(hpow(w_r, r2 * k1, m), scale, m);
+  return tc;
+}
+
+// Per-pass table T[r][k] = w_p^(r k), r < R, k < ns (w_p = w^(n/(ns R)), the pass's twiddle root)
+static Table pass_tab(uint64_t w_p, uint64_t R, uint64_t ns, uint64_t m) {
+  Table t;
+  t.reserve(R * ns);
+  for (uint64_t r = 0; r < R; ++r) {
+    const Table row = geometric(1, hpow(w_p, r, m), ns, m);
+    t.insert(t.end(), row.begin(), row.end());
+  }
+  return t;
+}
+
+// The same twiddles split for a last pass: w_p^(r k) = B[kb][r] * A[r][c] for k = kb W + c, with
+// A[r][c] = w_p^(r c) (R x W) and B[kb][r] = w_p^(r kb W) (ns/W x R)
+static std::pair<Table, Table> split_tabs(uint64_t w_p, uint64_t R, uint64_t W, uint64_t ns, uint64_t m) {
+  Table ta = pass_tab(w_p, R, W, m), tb((ns / W) * R);
+  for (uint64_t r = 0; r < R; ++r) {
+    const Table col = geometric(1, hpow(w_p, r * W, m), ns / W, m);
+    for (uint64_t kb = 0; kb < ns / W; ++kb) tb[kb * R + r] = col[kb];
+  }
+  return {ta, tb};
+}
+
 // radix bits per pass: option "ntt.passes" (e.g. "12,12"; every radix family the planner can
 // pick, tests/test_ntt_gpu.py), else passes of at most 2^10 as equal as possible
 static std::vector<int> default_passes(uint32_t log_n, const Options& o) {
@@ -82,8 +131,10 @@ static std::vector<int> default_passes(uint32_t log_n, const Options& o) {
   return v;
 }
 
-
-static int gl_tile(int logr);
+// Tile of R x W elements per workgroup of ntt_gl_pass_kernel: radix 2^10 8192 (W = 8: 64-B runs
+// in HBM, two workgroups per CU), smaller radices 4096 (W >= 16; four or five workgroups per CU).
+// Wider tiles (W = 16 at 2^10: one workgroup per CU) measured slower in round 4.
+static constexpr int gl_tile(int logr) { return logr >= 10 ? 8192 : 4096; }
 
 int make_plan(uint64_t m, uint64_t omega, uint64_t n, int inverse, NttPlan* p) {
   if (!field_for(m, &p->kind, &p->fa)) return fail(5, "unsupported modulus");
@@ -97,17 +148,15 @@ int make_plan(uint64_t m, uint64_t omega, uint64_t n, int inverse, NttPlan* p) {
     if (hpow(omega, n, m) != 1 || hpow(omega, n / 2, m) == 1) return fail(1, "omega does not have order n");
   }
   p->m = m; p->omega = omega; p->n = n; p->inverse = inverse; p->log_n = log_n;
-  uint64_t w = omega;
+  p->root = omega;
   if (inverse) {
     if (!hinv(n % m, m, &p->n_inv)) return fail(2, "n has no inverse modulo M (fft.rs:73 unwrap)");
-    if (!hinv(omega, m, &w)) return fail(1, "omega not invertible");
+    if (!hinv(omega, m, &p->root)) return fail(1, "omega not invertible");
   }
-  if (n <= 4096) {
-    std::vector<uint64_t> t(n);
-    uint64_t x = 1 % m;
-    for (uint64_t i = 0; i < n; ++i) { t[i] = x; x = hmul(x, w, m); }
-    return upload(p->small_tw, t);
-  }
+  const uint64_t w = p->root;
+  const long long tm = p->opts.num("ntt.twmax_log", 24);
+  p->twmax_log = (int)(tm < 0 ? 0 : (tm > 30 ? 30 : tm));
+  if (n <= 4096) return upload(p->small_tw, geometric(1, w, n, m));
   p->logr = default_passes(log_n, p->opts);
   p->tw_bits = (log_n + 1) / 2;
   // standard Goldilocks root => shift twiddles in the register sub-DFTs
@@ -117,147 +166,97 @@ int make_plan(uint64_t m, uint64_t omega, uint64_t n, int inverse, NttPlan* p) {
     if (w64 == hpow(2, 39, m)) p->e64 = 39;
     else if (w64 == hpow(2, 153, m)) p->e64 = 153;
   }
-  std::vector<uint64_t> t0(1ull << p->tw_bits), t1(n >> p->tw_bits);
-  uint64_t x = 1 % m;
-  for (size_t i = 0; i < t0.size(); ++i) { t0[i] = x; x = hmul(x, w, m); }
-  uint64_t step = x;  // w^(2^tw_bits)
-  x = 1 % m;
-  for (size_t i = 0; i < t1.size(); ++i) { t1[i] = x; x = hmul(x, step, m); }
-  int rc = upload(p->tw0, t0);
-  if (!rc) rc = upload(p->tw1, t1);
-  if (rc) return rc;
-  // per-pass [r][k] twiddle tables while R*Ns <= 2^ntt.twmax_log (default 24: the last
-  // pass of a 2^24 transform reads a 128 MiB table, shared by every polynomial of a batch,
-  // in 128-B runs like its data; the two-level table's two random gathers per element were
-  // bound by the texture unit: 2^24 x 2 0.545 -> 0.490 ms); larger passes
-  // use the two-level table
-  {
-    uint64_t ns = 1;
-    long long tm = p->opts.num("ntt.twmax_log", 24);
-    const int twmax = (int)(tm < 0 ? 0 : (tm > 30 ? 30 : tm));
-    for (size_t i = 0; i < p->logr.size(); ++i) {
-      const uint64_t R = 1ull << p->logr[i];
-      auto b = std::make_shared<DevBuf>();
-      if (ns > 1 && R * ns <= (1ull << twmax)) {
-        const uint64_t step = n / (ns * R);
-        std::vector<uint64_t> t(R * ns);
-        for (uint64_t r = 0; r < R; ++r) {
-          const uint64_t wr = hpow(w, step * r, m);  // (w^(step*r))^k
-          uint64_t z = 1 % m;
-          for (uint64_t kk = 0; kk < ns; ++kk) { t[r * ns + kk] = z; z = hmul(z, wr, m); }
-        }
-        int rc1 = upload(*b, t);
-        if (rc1) return rc1;
-      }
-      p->twpass.push_back(b);
-      // the last pass of a standard-root plan whose [r][k] table is not built: split table
-      // (option ntt.twsplit=1 also replaces a built one, =0 keeps the two-level table: the
-      // paths of n > 2^24 exercised at test sizes)
-      const bool last = i + 1 == p->logr.size();
-      const long long ts = p->opts.num("ntt.twsplit", -1);
-      const bool split = ts == 1;
-      if (last && ns > 1 && p->e64 >= 0 && ts != 0 && p->logr[i] >= 6 && p->logr[i] <= 10 && (!b->p || split)) {
-        const uint64_t W = (uint64_t)gl_tile(p->logr[i]) >> p->logr[i];
-        if (ns % W == 0) {
-          if (split) p->twpass.back() = std::make_shared<DevBuf>();
-          const uint64_t wp = hpow(w, n / (ns * R), m);
-          std::vector<uint64_t> ta(R * W), tb((ns / W) * R);
-          for (uint64_t r = 0; r < R; ++r) {
-            const uint64_t wr = hpow(wp, r, m);
-            uint64_t z = 1 % m;
-            for (uint64_t c = 0; c < W; ++c) { ta[r * W + c] = z; z = hmul(z, wr, m); }
-            const uint64_t wrw = hpow(wr, W, m);  // (w_p^r)^(kb W)
-            z = 1 % m;
-            for (uint64_t kb = 0; kb < ns / W; ++kb) { tb[kb * R + r] = z; z = hmul(z, wrw, m); }
-          }
-          p->tws_a = std::make_shared<DevBuf>();
-          p->tws_b = std::make_shared<DevBuf>();
-          int rc2 = upload(*p->tws_a, ta);
-          if (!rc2) rc2 = upload(*p->tws_b, tb);
-          if (rc2) return rc2;
-          p->tws_w = (int)W;
-        }
-      }
-      ns *= R;
-    }
-  }
-  for (int lr : p->logr) {
-    uint64_t R = 1ull << lr;
-    uint64_t wr = hpow(w, n / R, m);
-    std::vector<uint64_t> rt(R);
-    uint64_t y = 1 % m;
-    for (uint64_t i = 0; i < R; ++i) { rt[i] = y; y = hmul(y, wr, m); }
-    auto b = std::make_shared<DevBuf>();
-    rc = upload(*b, rt);
-    if (rc) return rc;
-    p->rtab.push_back(b);
-  }
-  // ntt_gl_pass_kernel (standard Goldilocks roots, radices 2^6..2^10): stage-C tables
-  // tc[r2][k1] = w_R^(r2*k1), r2 < R/64, k1 < 64; the last pass of an inverse carries n^-1
+  // ntt_gl_pass_kernel runs the plans of standard Goldilocks roots and radices 2^6..2^10,
+  // ntt_pass_kernel every other
   p->gl = p->e64 >= 0;
   for (int lr : p->logr) p->gl = p->gl && lr >= 6 && lr <= 10;
-  if (p->gl) {
-    for (size_t i = 0; i < p->logr.size(); ++i) {
-      const uint64_t R = 1ull << p->logr[i], C = R / 64;
-      const uint64_t wr = hpow(w, n / R, m);
-      const bool scaled = p->inverse && i + 1 == p->logr.size();
-      std::vector<uint64_t> tc(C * 64);
-      for (uint64_t r2 = 0; r2 < C; ++r2)
-        for (uint64_t k1 = 0; k1 < 64; ++k1) {
-          const uint64_t z = hpow(wr, r2 * k1, m);
-          tc[r2 * 64 + k1] = scaled ? hmul(z, p->n_inv, m) : z;
-        }
-      auto b = std::make_shared<DevBuf>();
-      rc = upload(*b, tc);
-      if (rc) return rc;
-      p->tc.push_back(b);
-    }
-  }
   // regrouped 2^24 plan (default for 8,8,8 standard-root plans; option ntt.no_rg=1 keeps the
   // round-2 passes, the tests' cross-check): three twiddle layers of order 4096, 2^18 and 2^24
   // 
-  if (p->gl && log_n == 24 && p->logr == std::vector<int>{8, 8, 8} && p->opts.num("ntt.no_rg", 0) == 0) p->rg = true;
+  p->rg = p->gl && log_n == 24 && p->logr == std::vector<int>{8, 8, 8} && p->opts.num("ntt.no_rg", 0) == 0;
+
+  int rc;
+  const auto tw = two_level_tabs(w, n, p->tw_bits, 1, m);
+  if ((rc = upload(p->tw0, tw.first)) || (rc = upload(p->tw1, tw.second))) return rc;
+  const size_t P = p->logr.size();
+  uint64_t ns = 1;
+  for (size_t i = 0; i < P; ++i) {
+    const uint64_t R = 1ull << p->logr[i], w_p = hpow(w, n / (ns * R), m);
+    // per-pass [r][k] twiddle tables while R*Ns <= 2^ntt.twmax_log (default 24: the last
+    // pass of a 2^24 transform reads a 128 MiB table, shared by every polynomial of a batch,
+    // in 128-B runs like its data; the two-level table's two random gathers per element were
+    // bound by the texture unit: 2^24 x 2 0.545 -> 0.490 ms); larger passes
+    // use the two-level table
+    p->twpass.push_back(std::make_shared<DevBuf>());
+    if (ns > 1 && R * ns <= (1ull << p->twmax_log) && (rc = upload(*p->twpass[i], pass_tab(w_p, R, ns, m)))) return rc;
+    // the last pass of a standard-root plan whose [r][k] table is not built: split table
+    // (option ntt.twsplit=1 also replaces a built one, =0 keeps the two-level table: the
+    // paths of n > 2^24 exercised at test sizes)
+    const long long ts = p->opts.num("ntt.twsplit", -1);
+    const uint64_t W = (uint64_t)gl_tile(p->logr[i]) >> p->logr[i];
+    if (i + 1 == P && ns > 1 && p->e64 >= 0 && ts != 0 && p->logr[i] >= 6 && p->logr[i] <= 10 &&
+        (!p->twpass[i]->p || ts == 1) && ns % W == 0) {
+      if (ts == 1) p->twpass[i] = std::make_shared<DevBuf>();
+      const auto ab = split_tabs(w_p, R, W, ns, m);
+      p->tws_a = std::make_shared<DevBuf>();
+      p->tws_b = std::make_shared<DevBuf>();
+      if ((rc = upload(*p->tws_a, ab.first)) || (rc = upload(*p->tws_b, ab.second))) return rc;
+      p->tws_w = (int)W;
+    }
+    ns *= R;
+  }
+  for (size_t i = 0; i < P; ++i) {
+    const uint64_t R = 1ull << p->logr[i], w_r = hpow(w, n / R, m);
+    auto b = std::make_shared<DevBuf>();
+    if (p->gl) {
+      // stage-C table of ntt_gl_pass_kernel; the last pass of an inverse carries n^-1
+      rc = upload(*b, stage_c_tab(w_r, R / 64, (inverse && i + 1 == P) ? p->n_inv : 1, m));
+      p->tc.push_back(b);
+    } else {
+      // w_R^m, m < R: the in-workgroup stage twiddles of ntt_pass_kernel
+      rc = upload(*b, geometric(1, w_r, R, m));
+      p->rtab.push_back(b);
+    }
+    if (rc) return rc;
+  }
   return 0;
 }
 
 // ---------------------------------------------------------------- dispatch
+// Calls fn(F{}) with F the device field type of `k`, so that a kernel's launch is written once
+// for both fields: with_field(k, [&](auto F) { ... kernel<decltype(F)> ... })
+template <class Fn>
+static auto with_field(FieldKind k, Fn&& fn) {
+  return k == FIELD_GOLDILOCKS ? fn(Goldilocks{}) : fn(Mod32{});
+}
+
 typedef void (*PassFn)(PassArgs);
 
-static int cols_for(int logr) {
+// W columns per workgroup of ntt_pass_kernel, one tile per workgroup (the LDS-DMA double-buffered
+// and register-prefetching persistent forms of rounds 1-2 measured slower and were removed in
+// round 6: DESIGN.md §3.2)
+static constexpr int cols_for(int logr) {
   // radix 2^10: 8 columns (64-KiB tile, two workgroups per CU overlap each other's HBM
   // and arithmetic phases; measured 0.548 vs 0.585 ms for 16 columns at 2^20 x 32)
   return logr < 10 ? 16 : (logr == 10 ? 8 : (logr == 11 ? 8 : 4));
 }
 
-// Kernel configuration of one pass: W columns, register radix 2^LQ, one tile per workgroup
-// (the LDS-DMA double-buffered and register-prefetching persistent forms of rounds 1-2 measured
-// slower and were removed in round 6: DESIGN.md §3.2)
-struct PassCfg {
-  int w, lq;
-};
-
-static PassCfg pass_cfg(int logr) { return PassCfg{cols_for(logr), 4}; }
-
-#define PBF_PASS(F, LR, W, LQ, E) \
-  if (logr == LR && c.w == W && c.lq == LQ) return ntt_pass_kernel<F, LR, W, ((W << LR) >> LQ), LQ, E>;
-
 template <class F, int E>
-static PassFn pass_fn_e(int logr, PassCfg c) {
-  PBF_PASS(F, 10, 8, 4, E)
-  PBF_PASS(F, 11, 8, 4, E)
-  PBF_PASS(F, 12, 4, 4, E)
-  PBF_PASS(F, 6, 16, 4, E)
-  PBF_PASS(F, 7, 16, 4, E)
-  PBF_PASS(F, 8, 16, 4, E)
-  PBF_PASS(F, 9, 16, 4, E)
-  return nullptr;
+static PassFn pass_fn_e(int logr) {
+#define PBF_PASS(LR) \
+  case LR: return ntt_pass_kernel<F, LR, cols_for(LR), ((cols_for(LR) << LR) >> NTT_LQ), E>;
+  switch (logr) {
+    PBF_PASS(6) PBF_PASS(7) PBF_PASS(8) PBF_PASS(9) PBF_PASS(10) PBF_PASS(11) PBF_PASS(12)
+    default: return nullptr;
+  }
+#undef PBF_PASS
 }
 
-static PassFn pass_fn(FieldKind k, int e64, int logr, PassCfg c) {
-  if (k == FIELD_MOD32) return pass_fn_e<Mod32, -1>(logr, c);
-  if (e64 == 39) return pass_fn_e<Goldilocks, 39>(logr, c);
-  if (e64 == 153) return pass_fn_e<Goldilocks, 153>(logr, c);
-  return pass_fn_e<Goldilocks, -1>(logr, c);
+static PassFn pass_fn(FieldKind k, int e64, int logr) {
+  if (k == FIELD_MOD32) return pass_fn_e<Mod32, -1>(logr);
+  if (e64 == 39) return pass_fn_e<Goldilocks, 39>(logr);
+  if (e64 == 153) return pass_fn_e<Goldilocks, 153>(logr);
+  return pass_fn_e<Goldilocks, -1>(logr);
 }
 
 // A coset transform on the ntt_gl_pass_kernel passes (run_plan_coset): the factor table and,
@@ -320,13 +319,9 @@ int make_two_level(uint64_t m, uint64_t root, uint64_t n, TwoLevel* t) {
   while ((1ull << log_n) < n) ++log_n;
   t->bits = (log_n + 1) / 2;
   t->root = root;
-  std::vector<uint64_t> t0(1ull << t->bits), t1((n >> t->bits) ? (n >> t->bits) : 1);
-  uint64_t x = 1 % m;
-  for (size_t i = 0; i < t0.size(); ++i) { t0[i] = x; x = hmul(x, root, m); }
-  uint64_t step = x, y = 1 % m;
-  for (size_t i = 0; i < t1.size(); ++i) { t1[i] = y; y = hmul(y, step, m); }
-  int rc = upload(t->t0, t0);
-  return rc ? rc : upload(t->t1, t1);
+  const auto tw = two_level_tabs(root, n, t->bits, 1, m);
+  int rc = upload(t->t0, tw.first);
+  return rc ? rc : upload(t->t1, tw.second);
 }
 
 template <class F>
@@ -361,60 +356,74 @@ static int combine_typed(const FieldArgs& fa, const TwoLevel& tl, uint32_t G, ui
 
 int launch_shard_combine(FieldKind k, const FieldArgs& fa, const TwoLevel& tl, uint32_t G, uint64_t rank,
                          const uint64_t* in, uint64_t* out, uint64_t nl, uint32_t batch, int inverse, hipStream_t s) {
-  if (k == FIELD_GOLDILOCKS) return combine_typed<Goldilocks>(fa, tl, G, rank, in, out, nl, batch, inverse, s);
-  return combine_typed<Mod32>(fa, tl, G, rank, in, out, nl, batch, inverse, s);
+  return with_field(k, [&](auto F) {
+    return combine_typed<decltype(F)>(fa, tl, G, rank, in, out, nl, batch, inverse, s);
+  });
 }
 
 typedef void (*GlPassFn)(GlPassArgs);
 
-// Tile of R x W elements per workgroup: radix 2^10 8192 (W = 8: 64-B runs in HBM, two
-// workgroups per CU), smaller radices 4096 (W >= 16; four or five workgroups per CU). Wider
-// tiles (W = 16 at 2^10: one workgroup per CU) measured slower in round 4.
-static int gl_tile(int logr) { return logr >= 10 ? 8192 : 4096; }
+// Which ntt_gl_* kernel one pass of a plan runs (the template parameters of ntt_gl.hpp); the
+// tile is gl_tile(logr).
+struct GlPassDesc {
+  int logr;
+  bool first;
+  int rg;  // regrouped 2^24 plan: pass 1, 2 (ntt_gl_rg2_kernel) or 3; 0 = not regrouped
+  int cs;  // coset variant: 1 = scales its loads, 2 = scales its stores
+  int sp;  // specialised second pass of a plain forward two-pass plan: 1, or 2 for equal radices
+};
+
+// Two-pass plans apply the second pass's twiddle w^(j k) at the first pass's stores (post_tw,
+// gl_pass_args), when that pass has its [r][k] table and stores no split layout
+static bool two_pass_tw(const NttPlan& p, uint32_t split_log) {
+  return p.logr.size() == 2 && split_log == 0 && p.twpass[1]->p;
+}
+
+static GlPassDesc gl_pass_desc(const NttPlan& p, size_t i, bool coset, uint32_t split_log) {
+  const size_t P = p.logr.size();
+  GlPassDesc d{p.logr[i], i == 0, 0, 0, 0};
+  // the regrouped plan stores no split layout
+  if (p.rg && P == 3 && split_log == 0) d.rg = (int)i + 1;
+  // coset: a forward transform's first pass scales its loads, an inverse's last pass its stores
+  if (coset && !p.inverse && i == 0) d.cs = 1;
+  if (coset && p.inverse && i == P - 1) d.cs = 2;
+  // plain forward two-pass plans whose second pass is radix 2^10 (the 2^20 default "10,10") and
+  // skips its twiddle: that pass compiled with only what such a plan executes (ntt_gl.hpp SP);
+  // instantiated for the forward standard root only. Equal radices: its log_ns is the constant 10.
+  if (two_pass_tw(p, split_log) && i == 1 && !coset && !p.inverse && p.e64 == 39 && d.logr == 10)
+    d.sp = p.logr[0] == 10 ? 2 : 1;
+  return d;
+}
+
+// The kernel of a descriptor: exactly the instantiations gl_pass_desc can ask for.
+template <int E, int LR>
+static GlPassFn gl_kernel_lr(const GlPassDesc& d) {
+  constexpr int T = gl_tile(LR);
+  if (d.first) return d.cs ? ntt_gl_pass_kernel<LR, E, true, T, 0, 1> : ntt_gl_pass_kernel<LR, E, true, T>;
+  return d.cs ? ntt_gl_pass_kernel<LR, E, false, T, 0, 2> : ntt_gl_pass_kernel<LR, E, false, T>;
+}
 
 template <int E>
-static GlPassFn gl_fn_e(int logr, bool first) {
-  switch (logr) {
-    case 6: return first ? ntt_gl_pass_kernel<6, E, true, 4096> : ntt_gl_pass_kernel<6, E, false, 4096>;
-    case 7: return first ? ntt_gl_pass_kernel<7, E, true, 4096> : ntt_gl_pass_kernel<7, E, false, 4096>;
-    case 8: return first ? ntt_gl_pass_kernel<8, E, true, 4096> : ntt_gl_pass_kernel<8, E, false, 4096>;
-    case 9: return first ? ntt_gl_pass_kernel<9, E, true, 4096> : ntt_gl_pass_kernel<9, E, false, 4096>;
-    case 10: return first ? ntt_gl_pass_kernel<10, E, true, 8192> : ntt_gl_pass_kernel<10, E, false, 8192>;
+static GlPassFn gl_kernel_e(const GlPassDesc& d) {
+  if (d.rg == 1) return d.cs ? ntt_gl_pass_kernel<8, E, true, 4096, 1, 1> : ntt_gl_pass_kernel<8, E, true, 4096, 1>;
+  if (d.rg == 2) return ntt_gl_rg2_kernel<E>;
+  if (d.rg == 3) return d.cs ? ntt_gl_pass_kernel<8, E, false, 4096, 3, 2> : ntt_gl_pass_kernel<8, E, false, 4096, 3>;
+  if constexpr (E == 39) {
+    if (d.sp == 1) return ntt_gl_pass_kernel<10, E, false, 8192, 0, 0, 1>;
+    if (d.sp == 2) return ntt_gl_pass_kernel<10, E, false, 8192, 0, 0, 2>;
+  }
+  switch (d.logr) {
+    case 6: return gl_kernel_lr<E, 6>(d);
+    case 7: return gl_kernel_lr<E, 7>(d);
+    case 8: return gl_kernel_lr<E, 8>(d);
+    case 9: return gl_kernel_lr<E, 9>(d);
+    case 10: return gl_kernel_lr<E, 10>(d);
     default: return nullptr;
   }
 }
 
-// coset variants (ntt_gl.hpp CS): 1 = first pass scaling its loads, 2 = last pass scaling its stores
-template <int E>
-static GlPassFn gl_fn_cs(int logr, int cs) {
-  switch (logr) {
-    case 6: return cs == 1 ? ntt_gl_pass_kernel<6, E, true, 4096, 0, 1> : ntt_gl_pass_kernel<6, E, false, 4096, 0, 2>;
-    case 7: return cs == 1 ? ntt_gl_pass_kernel<7, E, true, 4096, 0, 1> : ntt_gl_pass_kernel<7, E, false, 4096, 0, 2>;
-    case 8: return cs == 1 ? ntt_gl_pass_kernel<8, E, true, 4096, 0, 1> : ntt_gl_pass_kernel<8, E, false, 4096, 0, 2>;
-    case 9: return cs == 1 ? ntt_gl_pass_kernel<9, E, true, 4096, 0, 1> : ntt_gl_pass_kernel<9, E, false, 4096, 0, 2>;
-    case 10: return cs == 1 ? ntt_gl_pass_kernel<10, E, true, 8192, 0, 1> : ntt_gl_pass_kernel<10, E, false, 8192, 0, 2>;
-    default: return nullptr;
-  }
-}
-
-// plain forward two-pass plans whose second pass is radix 2^10 (the 2^20 default "10,10"): that
-// pass compiled with only what such a plan executes (ntt_gl.hpp SP). same_radix: the first pass
-// is radix 2^10 too, so the second pass's log_ns is the constant 10.
-static GlPassFn gl_fn_sp10(bool same_radix) {
-  return same_radix ? ntt_gl_pass_kernel<10, 39, false, 8192, 0, 0, 2> : ntt_gl_pass_kernel<10, 39, false, 8192, 0, 0, 1>;
-}
-
-// the regrouped 2^24 plan's three pass kernels
-template <int E>
-static GlPassFn gl_fn_rg(int pass) {
-  if (pass == 0) return ntt_gl_pass_kernel<8, E, true, 4096, 1>;
-  if (pass == 1) return ntt_gl_rg2_kernel<E>;
-  return ntt_gl_pass_kernel<8, E, false, 4096, 3>;
-}
-// and its first / last pass as coset variants (cs 1 / 2)
-template <int E>
-static GlPassFn gl_fn_rg_cs(int cs) {
-  return cs == 1 ? ntt_gl_pass_kernel<8, E, true, 4096, 1, 1> : ntt_gl_pass_kernel<8, E, false, 4096, 3, 2>;
+static GlPassFn gl_kernel(const GlPassDesc& d, int e64) {
+  return e64 == 39 ? gl_kernel_e<39>(d) : gl_kernel_e<153>(d);
 }
 
 // Passes of a standard-root Goldilocks plan through ntt_gl_pass_kernel (ntt_gl.hpp).
@@ -516,9 +525,7 @@ static int run_gl_passes(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out
 static int ensure_rg_tables(const NttPlan& p) {
   if (p.rg_built) return 0;
   const uint64_t m = p.m, n = p.n;
-  const int inverse = p.inverse;
-  uint64_t w = p.omega;  // the transform's root: omega, or omega^-1 for the inverse (make_plan)
-  if (inverse && !hinv(p.omega, m, &w)) return fail(1, "omega not invertible");
+  const uint64_t w = p.root;
   int rc;
   const uint64_t w4096 = hpow(w, n / 4096, m);
   std::vector<uint64_t> tc1(4096);
@@ -526,15 +533,10 @@ static int ensure_rg_tables(const NttPlan& p) {
     for (uint64_t r2 = 0; r2 < 4; ++r2)
       for (uint64_t k1 = 0; k1 < 64; ++k1)
         tc1[a2l * 256 + r2 * 64 + k1] = hpow(w4096, ((a2l + 16 * r2) * k1) % 4096, m);
-  std::vector<uint64_t> t2(1ull << 18);
-  for (uint64_t a1 = 0; a1 < 64; ++a1) {
-    const uint64_t st = hpow(w, 64 * a1, m);
-    uint64_t y = 1;
-    for (uint64_t K = 0; K < 4096; ++K) { t2[(a1 << 12) + K] = y; y = hmul(y, st, m); }
-  }
+  const Table t2 = pass_tab(hpow(w, 64, m), 64, 4096, m);  // t2[a1][K] = w^(64 a1 K)
   // the last pass's twiddle w^(a0 X) (a0 = r2 + 4 s2, X = 65536 f + j) as C[r2][X] D[X]^s2 (round
   // 5: from 10 MiB instead of a 2^24-entry, 128 MiB table T3[f][a0][j], profiles/r05/t3geo_ab.log)
-  const uint64_t scale = inverse ? p.n_inv : 1;
+  const uint64_t scale = p.inverse ? p.n_inv : 1;
   std::vector<uint64_t> tgc(4ull << 18), tgb(1ull << 18);
   {
     const uint64_t w4 = hpow(w, 4, m);
@@ -557,97 +559,100 @@ static int ensure_rg_tables(const NttPlan& p) {
   return 0;
 }
 
+// The arguments of pass i (descriptor d, log_ns = log2 of the product of the earlier radices) over
+// `batch` polynomials from `in` to `out`.
+static GlPassArgs gl_pass_args(const NttPlan& p, size_t i, const GlPassDesc& d, uint32_t log_ns, const uint64_t* in,
+                               uint64_t* out, size_t batch, uint32_t split_log, const GlCoset* cs) {
+  const bool last = i == p.logr.size() - 1;
+  const uint64_t W = (uint64_t)gl_tile(d.logr) >> d.logr;
+  GlPassArgs a;
+  a.in = in;
+  a.out = out;
+  a.in_pitch = a.out_pitch = p.n;
+  a.twpass = (const uint64_t*)p.twpass[i]->p;
+  a.tw0 = (const uint64_t*)p.tw0.p;
+  a.tw1 = (const uint64_t*)p.tw1.p;
+  a.tc = (const uint64_t*)p.tc[i]->p;
+  const bool tws = !a.twpass && last && p.tws_a && (uint64_t)p.tws_w == W;
+  a.tws_a = tws ? (const uint64_t*)p.tws_a->p : nullptr;
+  a.tws_b = tws ? (const uint64_t*)p.tws_b->p : nullptr;
+  a.n = p.n;
+  a.log_n = p.log_n;
+  a.log_ns = log_ns;
+  a.tw_bits = p.tw_bits;
+  a.blocks_per_poly = (uint32_t)((p.n >> d.logr) / W);
+  a.batch = (uint32_t)batch;
+  a.scaled = (p.inverse && last) ? 1 : 0;
+  a.out_split_log = last ? split_log : 0;
+  const uint64_t tiles = (uint64_t)a.blocks_per_poly * batch;
+  // tile order (gl_tile_coords): later passes XCD k-major (the pass-twiddle table's slices
+  // fetched into each XCD's L2 once per pass, not once per polynomial)
+  a.xcd_kmajor = (log_ns > 0 && batch > 1 && tiles % 8 == 0) ? 1 : 0;
+  // two-pass plans apply the second pass's twiddle w^(j k) at the first pass's stores (the
+  // first pass hides the product under its memory phase: 2^20 x 32 0.400 -> 0.386 ms,
+  // DESIGN.md §3.1), reading that table by column in XCD k-major order too (round 4: 2^20 x 32
+  // 0.354-0.357 ms against 0.368-0.371 linear, profiles/r04/ntt_orders_sweep.log)
+  a.post_tw = nullptr;
+  a.skip_pass_tw = 0;
+  if (two_pass_tw(p, split_log)) {
+    if (i == 0) a.post_tw = (const uint64_t*)p.twpass[1]->p;
+    else a.skip_pass_tw = 1;
+  }
+  if (a.post_tw && batch > 1 && tiles % 8 == 0) a.xcd_kmajor = 1;
+  a.cs_tab = a.cs_tab1 = nullptr;
+  a.cs_bits = 0;
+  a.cs_len = 0;
+  if (d.cs) {
+    a.cs_tab = (const uint64_t*)cs->tabs->t0.p;
+    a.cs_tab1 = (const uint64_t*)cs->tabs->t1.p;
+    a.cs_bits = cs->tabs->bits;
+    if (d.cs == 1) {
+      a.cs_len = cs->in_len;
+      a.in_pitch = cs->in_len;
+    } else if (!d.rg) {
+      a.tc = (const uint64_t*)cs->tabs->tc_last.p;  // n^-1 rides in the factor table
+      a.scaled = 0;
+    }  // (the regrouped plan's last pass keeps n^-1 in its own table: ensure_rg_tables)
+  }
+  if (d.rg) {
+    if (d.rg == 1) a.tc = (const uint64_t*)p.rg_tc1.p;
+    if (d.rg == 2) a.twpass = (const uint64_t*)p.rg_t2.p;
+    if (d.rg == 3) {
+      a.twpass = nullptr;
+      a.tws_a = (const uint64_t*)p.rg_tgc.p;
+      a.tws_b = (const uint64_t*)p.rg_tgb.p;
+    }
+    // XCD-blocked order in every pass of the regrouped plan (round 4: 2 x 2^24 0.433-0.437 ms
+    // against 0.447-0.453 k-major, 0.462-0.466 linear, profiles/r04/ntt_order24_ab.log; round
+    // 5 with the geometric last pass 0.3867-0.3868 against 0.3918-0.3930, order_geo.log)
+    if (tiles % 8 == 0) a.xcd_kmajor = 2;
+  }
+  return a;
+}
+
 static int run_gl_group(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out, size_t batch, DevBuf& s0,
                         DevBuf& s1, hipStream_t stream, uint32_t split_log, size_t soff, const GlCoset* cs) {
   const size_t P = p.logr.size();
-  const bool rg = p.rg && P == 3 && split_log == 0;
   if (cs && (split_log != 0 || P < 2)) return fail(1, "coset transform: unsupported plan");
-  if (rg) {
+  if (gl_pass_desc(p, 0, cs != nullptr, split_log).rg) {
     const int rc = ensure_rg_tables(p);
     if (rc) return rc;
   }
   uint32_t log_ns = 0;
   for (size_t i = 0; i < P; ++i) {
-    const int lr = p.logr[i];
-    const int tile = gl_tile(lr);
-    GlPassFn fn = p.e64 == 39 ? gl_fn_e<39>(lr, log_ns == 0) : gl_fn_e<153>(lr, log_ns == 0);
-    if (rg) fn = p.e64 == 39 ? gl_fn_rg<39>((int)i) : gl_fn_rg<153>((int)i);
-    // coset: a forward transform's first pass scales its loads, an inverse's last pass its stores
-    const int csv = !cs ? 0 : (!p.inverse && i == 0) ? 1 : (p.inverse && i == P - 1) ? 2 : 0;
-    if (csv && rg) fn = p.e64 == 39 ? gl_fn_rg_cs<39>(csv) : gl_fn_rg_cs<153>(csv);
-    else if (csv) fn = p.e64 == 39 ? gl_fn_cs<39>(lr, csv) : gl_fn_cs<153>(lr, csv);
-    // two-pass plans whose first pass applies the second pass's twiddle (post_tw below)
-    const bool two_pass_tw = P == 2 && split_log == 0 && p.twpass[1]->p;
-    if (two_pass_tw && i == 1 && !cs && !p.inverse && p.e64 == 39 && lr == 10) fn = gl_fn_sp10(p.logr[0] == 10);
+    const GlPassDesc d = gl_pass_desc(p, i, cs != nullptr, split_log);
+    const GlPassFn fn = gl_kernel(d, p.e64);
     if (!fn) return fail(1, "no Goldilocks pass kernel for this radix");
-    const uint64_t W = (uint64_t)tile >> lr;
-    if ((p.n >> lr) % W) return fail(1, "transform too small for the pass tile");
-    GlPassArgs a;
-    a.in = (i == 0) ? d_in : (const uint64_t*)(((i - 1) & 1) ? s1.p : s0.p) + soff;
-    a.out = (i == P - 1) ? d_out : (uint64_t*)((i & 1) ? s1.p : s0.p) + soff;
-    a.in_pitch = a.out_pitch = p.n;
-    a.twpass = (const uint64_t*)p.twpass[i]->p;
-    a.tw0 = (const uint64_t*)p.tw0.p;
-    a.tw1 = (const uint64_t*)p.tw1.p;
-    a.tc = (const uint64_t*)p.tc[i]->p;
-    const bool tws = !a.twpass && i == P - 1 && p.tws_a && (uint64_t)p.tws_w == W;
-    a.tws_a = tws ? (const uint64_t*)p.tws_a->p : nullptr;
-    a.tws_b = tws ? (const uint64_t*)p.tws_b->p : nullptr;
-    a.n = p.n;
-    a.log_n = p.log_n;
-    a.log_ns = log_ns;
-    a.tw_bits = p.tw_bits;
-    a.blocks_per_poly = (uint32_t)((p.n >> lr) / W);
-    a.batch = (uint32_t)batch;
-    a.scaled = (p.inverse && i == P - 1) ? 1 : 0;
-    a.out_split_log = (i == P - 1) ? split_log : 0;
+    const int tile = gl_tile(d.logr);
+    if ((p.n >> d.logr) % (tile >> d.logr)) return fail(1, "transform too small for the pass tile");
+    const uint64_t* in = (i == 0) ? d_in : (const uint64_t*)(((i - 1) & 1) ? s1.p : s0.p) + soff;
+    uint64_t* out = (i == P - 1) ? d_out : (uint64_t*)((i & 1) ? s1.p : s0.p) + soff;
+    const GlPassArgs a = gl_pass_args(p, i, d, log_ns, in, out, batch, split_log, cs);
     const uint64_t tiles = (uint64_t)a.blocks_per_poly * batch;
     if (tiles > 0x7fffffffull) return fail(1, "batch too large");
-    // tile order (gl_tile_coords): later passes XCD k-major (the pass-twiddle table's slices
-    // fetched into each XCD's L2 once per pass, not once per polynomial)
-    a.xcd_kmajor = (log_ns > 0 && batch > 1 && tiles % 8 == 0) ? 1 : 0;
-    // two-pass plans apply the second pass's twiddle w^(j k) at the first pass's stores (the
-    // first pass hides the product under its memory phase: 2^20 x 32 0.400 -> 0.386 ms,
-    // DESIGN.md §3.1), reading that table by column in XCD k-major order too (round 4: 2^20 x 32
-    // 0.354-0.357 ms against 0.368-0.371 linear, profiles/r04/ntt_orders_sweep.log)
-    a.post_tw = nullptr;
-    a.skip_pass_tw = 0;
-    if (two_pass_tw) {
-      if (i == 0) a.post_tw = (const uint64_t*)p.twpass[1]->p;
-      else a.skip_pass_tw = 1;
-    }
-    if (a.post_tw && batch > 1 && tiles % 8 == 0) a.xcd_kmajor = 1;
-    a.cs_tab = a.cs_tab1 = nullptr;
-    a.cs_bits = 0;
-    a.cs_len = 0;
-    if (csv) {
-      a.cs_tab = (const uint64_t*)cs->tabs->t0.p;
-      a.cs_tab1 = (const uint64_t*)cs->tabs->t1.p;
-      a.cs_bits = cs->tabs->bits;
-      if (csv == 1) {
-        a.cs_len = cs->in_len;
-        a.in_pitch = cs->in_len;
-      } else if (!rg) {
-        a.tc = (const uint64_t*)cs->tabs->tc_last.p;  // n^-1 rides in the factor table
-        a.scaled = 0;
-      }  // (the regrouped plan's last pass keeps n^-1 in its own table: ensure_rg_tables)
-    }
-    if (rg) {
-      if (i == 0) a.tc = (const uint64_t*)p.rg_tc1.p;
-      if (i == 1) a.twpass = (const uint64_t*)p.rg_t2.p;
-      if (i == 2) {
-        a.twpass = nullptr;
-        a.tws_a = (const uint64_t*)p.rg_tgc.p;
-        a.tws_b = (const uint64_t*)p.rg_tgb.p;
-      }
-      // XCD-blocked order in every pass of the regrouped plan (round 4: 2 x 2^24 0.433-0.437 ms
-      // against 0.447-0.453 k-major, 0.462-0.466 linear, profiles/r04/ntt_order24_ab.log; round
-      // 5 with the geometric last pass 0.3867-0.3868 against 0.3918-0.3930, order_geo.log)
-      if (tiles % 8 == 0) a.xcd_kmajor = 2;
-    }
     hipLaunchKernelGGL(fn, dim3((uint32_t)tiles), dim3(tile / 16), 0, stream, a);
     PBF_HIP(hipGetLastError());
-    log_ns += lr;
+    log_ns += d.logr;
   }
   return 0;
 }
@@ -660,12 +665,10 @@ static int run_plan_impl(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out
     return 0;  // size-1 DFT is the identity; n^-1 = 1
   }
   if (p.logr.empty()) {
-    if (p.kind == FIELD_GOLDILOCKS)
-      hipLaunchKernelGGL(ntt_small_kernel<Goldilocks>, dim3(batch), dim3(256), 0, stream, d_in, d_out,
+    with_field(p.kind, [&](auto F) {
+      hipLaunchKernelGGL(ntt_small_kernel<decltype(F)>, dim3(batch), dim3(256), 0, stream, d_in, d_out,
                          (const uint64_t*)p.small_tw.p, p.log_n, p.n_inv, (uint32_t)p.inverse, p.fa);
-    else
-      hipLaunchKernelGGL(ntt_small_kernel<Mod32>, dim3(batch), dim3(256), 0, stream, d_in, d_out,
-                         (const uint64_t*)p.small_tw.p, p.log_n, p.n_inv, (uint32_t)p.inverse, p.fa);
+    });
     PBF_HIP(hipGetLastError());
     return 0;
   }
@@ -679,22 +682,15 @@ static int run_plan_impl(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out
   if (cs) return fail(1, "coset transform: not a Goldilocks standard-root plan");
   for (size_t i = 0; i < P; ++i) {
     const int lr = p.logr[i];
-    PassCfg cfg = pass_cfg(lr);
-    PassFn fn = pass_fn(p.kind, p.e64, lr, cfg);
-    for (int w : {16, 8, 4}) {  // robust fallback: any instantiated single-tile shape
-      if (fn) break;
-      cfg = PassCfg{w, 4};
-      fn = pass_fn(p.kind, p.e64, lr, cfg);
-    }
+    const PassFn fn = pass_fn(p.kind, p.e64, lr);
     if (!fn) return fail(1, "no kernel for this radix");
-    const int W = cfg.w;
+    const int W = cols_for(lr);
     PassArgs a;
     a.in = (i == 0) ? d_in : (const uint64_t*)(((i - 1) & 1) ? s1.p : s0.p);
     a.out = (i == P - 1) ? d_out : (uint64_t*)((i & 1) ? s1.p : s0.p);
     a.tw0 = (const uint64_t*)p.tw0.p;
     a.tw1 = (const uint64_t*)p.tw1.p;
     a.rtab = (const uint64_t*)p.rtab[i]->p;
-    a.twfull = nullptr;
     a.twpass = (const uint64_t*)p.twpass[i]->p;
     a.n = p.n;
     a.n_inv = p.n_inv;
@@ -704,10 +700,9 @@ static int run_plan_impl(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out
     a.blocks_per_poly = (uint32_t)((p.n >> lr) / W);
     a.scale = (p.inverse && i == P - 1) ? 1 : 0;
     a.out_split_log = (i == P - 1) ? split_log : 0;
-    a.dbg = 0;
     a.batch = (uint32_t)batch;
     a.f = p.fa;
-    const int nt = (W << lr) >> cfg.lq;
+    const int nt = (W << lr) >> NTT_LQ;
     const uint64_t blocks = (uint64_t)a.blocks_per_poly * batch;
     if (blocks > 0x7fffffffull) return fail(1, "batch too large");
     const uint32_t grid = (uint32_t)blocks;
@@ -759,34 +754,19 @@ static int coset_tabs(const NttPlan& p, uint64_t shift, uint64_t len, const Cose
     if (!hinv(shift, m, &s)) return fail(1, "shift has no inverse");
     if (p.gl && !p.rg) c = p.n_inv;
   }
-  long long tm = p.opts.num("ntt.twmax_log", 24);
-  const int twmax = (int)(tm < 0 ? 0 : (tm > 30 ? 30 : tm));
   int rc;
-  if (len <= (1ull << twmax)) {
-    std::vector<uint64_t> v(len);
-    uint64_t x = c;
-    for (uint64_t i = 0; i < len; ++i) { v[i] = x; x = hmul(x, s, m); }
+  if (len <= (1ull << p.twmax_log)) {
     t->bits = 0;
     t->t1.release();
-    if ((rc = upload(t->t0, v))) return rc;
+    if ((rc = upload(t->t0, geometric(c, s, len, m)))) return rc;
   } else {
     t->bits = (log2_ceil(len) + 1) / 2;
-    std::vector<uint64_t> v0(1ull << t->bits), v1(((len - 1) >> t->bits) + 1);
-    uint64_t x = c, y = 1 % m;
-    for (size_t i = 0; i < v0.size(); ++i) { v0[i] = x; x = hmul(x, s, m); }
-    const uint64_t step = hpow(s, 1ull << t->bits, m);
-    for (size_t i = 0; i < v1.size(); ++i) { v1[i] = y; y = hmul(y, step, m); }
-    if ((rc = upload(t->t0, v0)) || (rc = upload(t->t1, v1))) return rc;
+    const auto tw = two_level_tabs(s, len, t->bits, c, m);
+    if ((rc = upload(t->t0, tw.first)) || (rc = upload(t->t1, tw.second))) return rc;
   }
   if (p.gl && !p.rg && p.inverse && !t->tc_last.p) {
-    const uint64_t R = 1ull << p.logr.back(), C = R / 64;
-    uint64_t w;
-    if (!hinv(p.omega, m, &w)) return fail(1, "omega not invertible");
-    const uint64_t wr = hpow(w, p.n / R, m);
-    std::vector<uint64_t> tc(C * 64);
-    for (uint64_t r2 = 0; r2 < C; ++r2)
-      for (uint64_t k1 = 0; k1 < 64; ++k1) tc[r2 * 64 + k1] = hpow(wr, r2 * k1, m);
-    if ((rc = upload(t->tc_last, tc))) return rc;
+    const uint64_t R = 1ull << p.logr.back();
+    if ((rc = upload(t->tc_last, stage_c_tab(hpow(p.root, p.n / R, m), R / 64, 1, m)))) return rc;
   }
   t->len = len;
   t->stamp = ++p.coset_clock;
@@ -815,12 +795,10 @@ __global__ void coset_scale_kernel(const uint64_t* in, uint64_t in_len, uint64_t
 static int launch_coset_scale(const NttPlan& p, const CosetTabs& t, const uint64_t* in, uint64_t in_len, uint64_t* out,
                               uint64_t batch, hipStream_t s) {
   const dim3 grid((uint32_t)grid_for(p.n * batch));
-  if (p.kind == FIELD_GOLDILOCKS)
-    hipLaunchKernelGGL(coset_scale_kernel<Goldilocks>, grid, dim3(256), 0, s, in, in_len, out, p.n, batch,
+  with_field(p.kind, [&](auto F) {
+    hipLaunchKernelGGL(coset_scale_kernel<decltype(F)>, grid, dim3(256), 0, s, in, in_len, out, p.n, batch,
                        (const uint64_t*)t.t0.p, (const uint64_t*)t.t1.p, t.bits, p.fa);
-  else
-    hipLaunchKernelGGL(coset_scale_kernel<Mod32>, grid, dim3(256), 0, s, in, in_len, out, p.n, batch,
-                       (const uint64_t*)t.t0.p, (const uint64_t*)t.t1.p, t.bits, p.fa);
+  });
   PBF_HIP(hipGetLastError());
   return 0;
 }
@@ -851,10 +829,9 @@ int launch_pointwise_mul(FieldKind k, const FieldArgs& fa, const uint64_t* a, co
   uint64_t blocks = (count + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   if (blocks == 0) return 0;
-  if (k == FIELD_GOLDILOCKS)
-    hipLaunchKernelGGL(pointwise_mul_kernel<Goldilocks>, dim3(blocks), dim3(256), 0, s, a, b, c, count, fa);
-  else
-    hipLaunchKernelGGL(pointwise_mul_kernel<Mod32>, dim3(blocks), dim3(256), 0, s, a, b, c, count, fa);
+  with_field(k, [&](auto F) {
+    hipLaunchKernelGGL(pointwise_mul_kernel<decltype(F)>, dim3(blocks), dim3(256), 0, s, a, b, c, count, fa);
+  });
   PBF_HIP(hipGetLastError());
   return 0;
 }
@@ -914,17 +891,12 @@ int launch_poly_eval(FieldKind k, const FieldArgs& fa, const uint64_t* d_coeffs,
   const uint64_t chunks = (n + per_block - 1) / per_block;
   int rc = partial.ensure(chunks * nx * 8);
   if (rc) return rc;
-  if (k == FIELD_GOLDILOCKS) {
-    hipLaunchKernelGGL(poly_eval_partial<Goldilocks>, dim3(chunks * nx), dim3(EVAL_THREADS), 0, s, d_coeffs, n, d_xs,
-                       chunks, (uint64_t*)partial.p, fa);
-    hipLaunchKernelGGL(poly_eval_final<Goldilocks>, dim3((nx + 255) / 256), dim3(256), 0, s,
+  with_field(k, [&](auto F) {
+    hipLaunchKernelGGL(poly_eval_partial<decltype(F)>, dim3(chunks * nx), dim3(EVAL_THREADS), 0, s, d_coeffs, n,
+                       d_xs, chunks, (uint64_t*)partial.p, fa);
+    hipLaunchKernelGGL(poly_eval_final<decltype(F)>, dim3((nx + 255) / 256), dim3(256), 0, s,
                        (const uint64_t*)partial.p, chunks, nx, d_ys, fa);
-  } else {
-    hipLaunchKernelGGL(poly_eval_partial<Mod32>, dim3(chunks * nx), dim3(EVAL_THREADS), 0, s, d_coeffs, n, d_xs,
-                       chunks, (uint64_t*)partial.p, fa);
-    hipLaunchKernelGGL(poly_eval_final<Mod32>, dim3((nx + 255) / 256), dim3(256), 0, s, (const uint64_t*)partial.p,
-                       chunks, nx, d_ys, fa);
-  }
+  });
   PBF_HIP(hipGetLastError());
   return 0;
 }

@@ -15,7 +15,7 @@ from typing import Sequence
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# PBF_LIB: an alternative in-tree build (timing experiments, e.g. libpbf_nomath.so)
+# PBF_LIB: an alternative build of the library (A/B runs against another commit's libpbf.so)
 LIB_PATH = os.environ.get("PBF_LIB") or os.path.join(os.path.dirname(_HERE), "libpbf.so")
 
 GOLDILOCKS = 0xFFFFFFFF00000001

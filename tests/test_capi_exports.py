@@ -153,6 +153,20 @@ def test_every_kernel_has_a_launch():
     assert not unlaunched, unlaunched
 
 
+def test_no_build_switches_in_csrc():
+    """The library has one build. The only preprocessor conditionals in csrc/ tell the host pass
+    of a translation unit from the device pass (__HIP_DEVICE_COMPILE__); a macro that selects a
+    timing mode or overrides a tuned constant (the retired PBF_GL_NOMATH, PBF_RS_ITEMS, ...)
+    would be a second build that no test compiles."""
+    found = []
+    for fn, text in sorted(csrc_sources().items()):
+        for m in re.finditer(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b([^\n]*)", text, flags=re.M):
+            found.append((fn, m.group(1).strip()))
+    assert len(found) >= 4, found  # the search itself found the host / device conditionals
+    allowed = ("__HIP_DEVICE_COMPILE__", "defined(__HIP_DEVICE_COMPILE__)")
+    assert [f for f in found if f[1] not in allowed] == []
+
+
 def test_set_option_is_declared_with_its_names():
     src = open(HEADER).read()
     assert "pbf_ctx_set_option" in src

@@ -188,14 +188,11 @@ def test_coset_lde_identity_2p24(ctx):
     assert np.array_equal(back[:a.size], a) and not back[a.size:].any()
 
 
-def test_coset_regrouped_2p24_matches_stockham(ctx):
-    """the regrouped 2^24 plan's coset variants (first / last pass) give the bits of the 8,8,8
-    Stockham passes (context option ntt.no_rg), both directions, two polynomials"""
+def regrouped_2p24_matches_stockham(ctx, w):
     import torch
 
     n, batch, s = 1 << 24, 2, shift_of(GOLD, "random")
     in_len = n // 4 + 3
-    w = root(GOLD, n)
     d_in = to_dev(oracle.splitmix_field(GOLD, 4402, batch * in_len))
     stream = torch.cuda.current_stream().cuda_stream
     res = []
@@ -212,6 +209,18 @@ def test_coset_regrouped_2p24_matches_stockham(ctx):
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
     back = to_host(res[0][1]).reshape(batch, n)
     assert np.array_equal(back[:, :in_len].reshape(-1), to_host(d_in)) and not back[:, in_len:].any()
+
+
+def test_coset_regrouped_2p24_matches_stockham(ctx):
+    """the regrouped 2^24 plan's coset variants (first / last pass) give the bits of the 8,8,8
+    Stockham passes (context option ntt.no_rg), both directions, two polynomials"""
+    regrouped_2p24_matches_stockham(ctx, root(GOLD, 1 << 24))
+
+
+def test_coset_regrouped_2p24_inverse_root(ctx):
+    """the same with the inverse root, whose forward transform runs the w_64 = 2^153 kernels and
+    whose inverse the 2^39 ones: the regrouped coset first pass on 2^153 and last pass on 2^39"""
+    regrouped_2p24_matches_stockham(ctx, pow(root(GOLD, 1 << 24), GOLD - 2, GOLD))
 
 
 # ---- 7. argument errors, through the host entry points (they return before any launch)

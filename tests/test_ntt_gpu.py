@@ -4,6 +4,7 @@ Mirrors the reference's fft.rs tests (test_fft_cooley_turkey, test_ntt_poly_mul)
 and extends them to every size class the kernels have (small-kernel path,
 2-pass and 3-pass Stockham) and to BASELINE's full sizes (2^20, 2^24) through the
 golden digests plus size-independent properties (round trip, linearity)."""
+import functools
 import hashlib
 
 import numpy as np
@@ -160,6 +161,71 @@ def test_regrouped_2p24_matches_stockham(inverse):
         c.close()
     assert np.array_equal(outs[0], outs[1])
     assert np.array_equal(outs[0][0], oracle.ntt_gl_par(w, host[0], inverse=inverse))
+
+
+GL_VARIANT_SHIFT, GL_VARIANT_BATCH = 7, 2
+
+
+@functools.lru_cache(maxsize=None)
+def gl_variant_refs(logn, inverse_root):
+    """Inputs and oracle results shared by the cases of one size and root (7^((p-1)/n), whose
+    w_64 is 2^39, or its inverse, whose w_64 is 2^153): a batch of polynomials and,
+    per polynomial, the plain forward and inverse transforms, the coset forward transform of
+    its first n/4 + 3 coefficients (a[j] 7^j, zero padded) and the coset inverse (the inverse
+    times 7^-j), as tests/test_coset_ntt_gpu.py builds them."""
+    n, s = 1 << logn, GL_VARIANT_SHIFT
+    w, in_len = root(GOLD, n), (1 << logn) // 4 + 3
+    w = pow(w, GOLD - 2, GOLD) if inverse_root else w
+    host = np.stack([oracle.splitmix_field(GOLD, 1300 + 10 * logn + i, n) for i in range(GL_VARIANT_BATCH)])
+    s_inv, sp, si = pow(s, GOLD - 2, GOLD), [1], [1]
+    for _ in range(n - 1):
+        sp.append(sp[-1] * s % GOLD)
+        si.append(si[-1] * s_inv % GOLD)
+    mul = lambda a, p: np.array([int(x) * y % GOLD for x, y in zip(a, p)], dtype=np.uint64)
+    refs = {}
+    for inverse in (False, True):
+        refs[inverse, False] = np.stack([oracle.ntt_iter(GOLD, w, a, inverse=inverse) for a in host])
+    padded = lambda a: np.concatenate([mul(a[:in_len], sp), np.zeros(n - in_len, dtype=np.uint64)])
+    refs[False, True] = np.stack([oracle.ntt_iter(GOLD, w, padded(a)) for a in host])
+    refs[True, True] = np.stack([mul(f, si) for f in refs[True, False]])
+    return w, host, in_len, refs
+
+
+@pytest.mark.parametrize("coset", [False, True], ids=["plain", "coset"])
+@pytest.mark.parametrize("inverse", [False, True], ids=["fwd", "inv"])
+@pytest.mark.parametrize("inverse_root", [False, True], ids=["w", "w_inv"])
+@pytest.mark.parametrize("passes", ["6,7", "7,6", "6,8", "8,6", "6,9", "9,6", "6,10", "10,6"])
+def test_gl_pass_kernel_variants(passes, inverse_root, inverse, coset):
+    """Every ntt_gl_pass_kernel variant that the two-pass plans select (ntt_launch.hip
+    gl_pass_desc): each radix 2^6 .. 2^10 as a first and as a last pass, plain and as the coset
+    variant that scales its loads (forward first pass) or its stores (inverse last pass), at the
+    smallest size that has the plan, on a batch of 2 (the XCD k-major tile order where the tile
+    count allows it), bit-exact against the oracle. The kernels are compiled per w_64 = 2^39 or
+    2^153, and a direction fixes which of the two its root has, so each direction also runs with
+    the inverse root: a forward transform on 2^153 (coset: scaled loads) and an inverse on 2^39
+    (coset: scaled stores). With "10,10" at 2^20 and the regrouped 2^24 tests
+    (tests/test_coset_ntt_gpu.py has the coset ones) these are all the instantiations."""
+    import torch
+
+    logn = sum(int(x) for x in passes.split(","))
+    n, batch = 1 << logn, GL_VARIANT_BATCH
+    w, host, in_len, refs = gl_variant_refs(logn, inverse_root)
+    c = pbf.Context(0, options={"ntt.passes": passes})
+    try:
+        stream = torch.cuda.current_stream().cuda_stream
+        src = host[:, :in_len] if coset and not inverse else host
+        d_in = torch.from_numpy(np.ascontiguousarray(src).view(np.int64)).cuda()
+        d_out = torch.empty(batch * n, dtype=torch.int64, device="cuda")
+        if coset:
+            c.ntt_coset_batch_dev(GOLD, w, GL_VARIANT_SHIFT, d_in.data_ptr(), src.shape[1], d_out.data_ptr(), n, batch,
+                                  inverse=inverse, stream=stream)
+        else:
+            c.ntt_batch_dev(GOLD, w, d_in.data_ptr(), d_out.data_ptr(), n, batch, inverse=inverse, stream=stream)
+        torch.cuda.synchronize()
+        got = d_out.cpu().numpy().view(np.uint64).reshape(batch, n)
+    finally:
+        c.close()
+    assert np.array_equal(got, refs[inverse, coset])
 
 
 def test_batch_dev_matches_single(ctx):
