@@ -25,6 +25,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/pbf.h"
+#include "fr_host.hpp"
 #include "internal.hpp"
 
 namespace {
@@ -488,18 +489,7 @@ int host_mul_ntt_multi(Group* grp, const NttOps& ops,
   });
 }
 
-// BN254 r (little-endian u64 limbs): Fr inputs are canonical residues, as in the single-GPU calls
-bool fr_canonical(const uint64_t* v, size_t n) {
-  static const uint64_t R[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull,
-                                0x30644e72e131a029ull};
-  for (size_t i = 0; i < n; ++i) {
-    const uint64_t* x = v + 4 * i;
-    int k = 3;
-    while (k >= 0 && x[k] == R[k]) --k;
-    if (k < 0 || x[k] > R[k]) return false;
-  }
-  return true;
-}
+// Fr inputs are canonical residues (fr_host.hpp fr_canonical), as in the single-GPU calls
 // the _dev forms: every rank holds nl elements per polynomial, a power of two >= G (the
 // stride-shard layout and the per-peer blocks of nl / G)
 int check_nl(size_t nl, uint32_t G) {

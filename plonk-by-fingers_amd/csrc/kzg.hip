@@ -4,7 +4,7 @@
 //   commit   SRS::eval_at_s (plonk.rs:51-58): one fixed-base MSM per polynomial against the
 //            context's window table of the SRS (msm.hpp)
 //   open     y_b = p_b(z) and W = commit((sum_b w_b (p_b - y_b)) / (x - z)) (plonk.rs:429-446), on
-//            the prover's own kernels (kzg.hpp): the chunked Horner evaluation, a linear
+//            the prover's own kernels (prover.hpp): the chunked Horner evaluation, a linear
 //            combination, the blocked synthetic division k_hs1..3. The quotient does not depend
 //            on the subtracted constants (they only move the remainder, which is dropped), so
 //            the division runs on sum_b w_b p_b as it stands and has no failing case. A fused
@@ -19,7 +19,7 @@
 #include <cstring>
 #include <vector>
 #include "../../include/pbf.h"
-#include "kzg.hpp"
+#include "prover.hpp"
 
 using namespace pbf;
 
@@ -42,7 +42,7 @@ int open_sweeps(pbf_ctx* ctx, const uint64_t* d_polys, uint64_t len, uint64_t pi
       lens[b] = len;
       xs[b] = z;
     }
-    if ((rc = fr_eval_run(polys, lens, xs, g, ctx->partial, d_y + 4 * b0, s))) return rc;
+    if ((rc = fr_eval_run(polys, lens, xs, g, 0, ctx->partial, d_y + 4 * b0, s))) return rc;
   }
   if (len < 2) return 0;
   DevBuf &bc = ctx->buf("kzg.comb"), &br = ctx->buf("kzg.rem");
@@ -50,17 +50,18 @@ int open_sweeps(pbf_ctx* ctx, const uint64_t* d_polys, uint64_t len, uint64_t pi
   uint64_t* comb = (uint64_t*)bc.p;
   for (uint64_t b0 = 0; b0 < batch;) {
     const uint64_t* in[10];
+    const uint64_t lens[10] = {len, len, len, len, len, len, len, len, len, len};
     U256 c[10];
     int k = 0;
     if (b0) {  // the sum so far
       in[k] = comb;
-      c[k++] = Fr::to_mont(Fr::one_plain());
+      c[k++] = fr_one_m();
     }
     while (k < 10 && b0 < batch) {
       in[k] = d_polys + 4 * b0 * pitch;
       c[k++] = w[b0++];
     }
-    if ((rc = fr_lincomb_run(in, c, k, len, comb, s))) return rc;
+    if ((rc = fr_lincomb_run(k, in, lens, c, u256_zero(), comb, len, s))) return rc;
   }
   HsArgs ha;
   ha.p = comb;
@@ -133,28 +134,6 @@ __global__ void __launch_bounds__(256) k_kzg_vsum(const uint64_t* part, uint32_t
   if (t == 0) u256_to_u64(Fr::sub(u256_zero(), sh[0]), out);
 }
 
-// (x, q - y), the identity unchanged
-void neg_g1(const uint64_t* p, uint64_t* out) {
-  for (int i = 0; i < 8; ++i) out[i] = p[i];
-  const U256 y = u256_from_u64(p + 4);
-  if (Fq::is_zero(y)) return;
-  U256 d;
-  uint64_t borrow = 0;
-  for (int i = 0; i < 8; ++i) {
-    const uint64_t t = (uint64_t)Bn254FqParams::P[i] - y.w[i] - borrow;
-    d.w[i] = (uint32_t)t;
-    borrow = (t >> 63) & 1;
-  }
-  u256_to_u64(d, out + 4);
-}
-
-bool fr_canonical(const uint64_t* p) { return !Fr::geq_p(u256_from_u64(p)); }
-bool all_canonical(const uint64_t* p, size_t count) {
-  for (size_t i = 0; i < count; ++i)
-    if (!fr_canonical(p + 4 * i)) return false;
-  return true;
-}
-
 // every argument error of commit / open, before anything is enqueued
 int poly_args(pbf_ctx* ctx, const uint64_t* srs, size_t srs_m, const uint64_t* polys, size_t len, size_t pitch,
               size_t batch, size_t need) {
@@ -171,7 +150,7 @@ int open_args(pbf_ctx* ctx, const uint64_t* srs, size_t srs_m, const uint64_t* p
   int rc = poly_args(ctx, srs, srs_m, polys, len, pitch, batch, len ? len - 1 : 0);
   if (rc) return rc;
   if (!fr_canonical(z)) return fail(PBF_EINVAL, "z must be canonical");
-  if (!all_canonical(weights, batch)) return fail(PBF_EINVAL, "weights must be canonical");
+  if (!fr_canonical(weights, batch)) return fail(PBF_EINVAL, "weights must be canonical");
   return 0;
 }
 
@@ -197,8 +176,8 @@ extern "C" int pbf_poly_eval_fr256(pbf_ctx* ctx, const uint64_t* coeffs, size_t 
                                    uint64_t* ys) {
   if (!ctx || !coeffs || !xs || !ys) return fail(PBF_EINVAL, "null argument");
   if (n == 0 || nx == 0) return fail(PBF_EINVAL, "n and nx must be at least 1");
-  if (!all_canonical(xs, nx)) return fail(PBF_EINVAL, "evaluation point not canonical");
-  if (!all_canonical(coeffs, n)) return fail(PBF_EINVAL, "coefficient not canonical");
+  if (!fr_canonical(xs, nx)) return fail(PBF_EINVAL, "evaluation point not canonical");
+  if (!fr_canonical(coeffs, n)) return fail(PBF_EINVAL, "coefficient not canonical");
   PBF_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->host_stream();
   int rc;
@@ -210,7 +189,7 @@ extern "C" int pbf_poly_eval_fr256(pbf_ctx* ctx, const uint64_t* coeffs, size_t 
     const uint64_t* polys[2] = {(const uint64_t*)ctx->io0.p, (const uint64_t*)ctx->io0.p};
     const uint64_t lens[2] = {n, n};
     const U256 pt[2] = {Fr::to_mont(u256_from_u64(xs + 4 * i)), Fr::to_mont(u256_from_u64(xs + 4 * (i + g - 1)))};
-    if ((rc = fr_eval_run(polys, lens, pt, g, ctx->partial, (uint64_t*)ctx->io1.p + 4 * i, s))) return rc;
+    if ((rc = fr_eval_run(polys, lens, pt, g, 0, ctx->partial, (uint64_t*)ctx->io1.p + 4 * i, s))) return rc;
   }
   PBF_HIP(hipMemcpyAsync(ys, ctx->io1.p, nx * 32, hipMemcpyDeviceToHost, s));
   PBF_HIP(hipStreamSynchronize(s));
@@ -304,7 +283,7 @@ extern "C" int pbf_kzg_verify_bn254(pbf_ctx* ctx, const uint64_t* g2, size_t cou
   if (!ctx || !g2 || !commits || !z || !y || !w || !rho || !ok) return fail(PBF_EINVAL, "null argument");
   *ok = 0;
   if (count == 0 || count > ((size_t)1 << 20)) return fail(PBF_EINVAL, "count must be in 1 .. 2^20");
-  if (!all_canonical(z, count) || !all_canonical(y, count)) return fail(PBF_EINVAL, "z and y must be canonical");
+  if (!fr_canonical(z, count) || !fr_canonical(y, count)) return fail(PBF_EINVAL, "z and y must be canonical");
   for (size_t i = 0; i < count; ++i) {
     const uint64_t* r = rho + 4 * i;
     if (!fr_canonical(r) || !(r[0] | r[1] | r[2] | r[3])) return fail(PBF_EINVAL, "rho must be canonical and nonzero");

@@ -19,6 +19,7 @@
 #include <cstring>
 #include <vector>
 #include "../../include/pbf.h"
+#include "fr_host.hpp"
 #include "msm.hpp"
 #include "msm_l29.hpp"
 #include "msm_sort.hpp"
@@ -1440,11 +1441,6 @@ static bool host_fq_canonical(const uint64_t* v) {
   for (int i = 0; i < 4; ++i) { x.w[2 * i] = (uint32_t)v[i]; x.w[2 * i + 1] = (uint32_t)(v[i] >> 32); }
   return !Fq::geq_p(x);
 }
-static bool host_fr_canonical(const uint64_t* v) {
-  U256 x;
-  for (int i = 0; i < 4; ++i) { x.w[2 * i] = (uint32_t)v[i]; x.w[2 * i + 1] = (uint32_t)(v[i] >> 32); }
-  return !Fr::geq_p(x);
-}
 
 }  // namespace pbf
 
@@ -1457,7 +1453,7 @@ int pbf_msm_g1_bn254(pbf_ctx* ctx, const uint64_t* points, const uint64_t* scala
   if (!ctx || !out || (n && (!points || !scalars))) return fail(PBF_EINVAL, "null argument");
   for (size_t i = 0; i < n; ++i)
     if (!host_fq_canonical(points + 8 * i) || !host_fq_canonical(points + 8 * i + 4) ||
-        !host_fr_canonical(scalars + 4 * i))
+        !fr_canonical(scalars + 4 * i))
       return fail(PBF_EINVAL, "input not canonical");
   if (n == 0) { for (int i = 0; i < 8; ++i) out[i] = 0; return PBF_OK; }
   PBF_HIP(hipSetDevice(ctx->device));
@@ -1581,7 +1577,7 @@ int pbf_g1_bn254_mul_base_dev(pbf_ctx* ctx, const uint64_t* d_scalars, uint64_t*
 // SRS::create (plonk.rs:35-48): g1s = [G, G*s, G*s^2, ..., G*s^n] -> out has n+1 points
 int pbf_srs_create_bn254(pbf_ctx* ctx, const uint64_t* s, size_t n, uint64_t* out) {
   if (!ctx || !s || !out) return fail(PBF_EINVAL, "null argument");
-  if (!host_fr_canonical(s)) return fail(PBF_EINVAL, "s not canonical");
+  if (!fr_canonical(s)) return fail(PBF_EINVAL, "s not canonical");
   PBF_HIP(hipSetDevice(ctx->device));
   std::vector<uint64_t> pw((n + 1) * 4);
   U256 sm;

@@ -1,4 +1,4 @@
-// Device-side MSM entry points shared by msm.hip and the prover (prover.hip).
+// Device-side MSM entry points shared by msm.hip, the prover (prover.hip), the verifiers and kzg.hip.
 #pragma once
 #include "ec_bn254.hpp"
 #include "internal.hpp"
@@ -32,13 +32,6 @@ struct SnapItem {
   uint64_t words;
 };
 int snapshot_check(pbf_ctx* ctx, const char* consumer, const SnapItem* items, int k, hipStream_t s, bool* same);
-// Plonk::verify's preprocessing (prover.hip), shared by the single and the batched verifier:
-// pre = the commitments of q_m q_l q_r q_o q_c s_sigma_1..3 (canonical affine), from the
-// context's verification key when option verifier.vk allows and q, copies and the SRS equal
-// their snapshots, else recomputed. omega = fr_root_of_unity(log2 n), Montgomery form.
-U256 fr_root_of_unity(uint32_t log_n);
-int verifier_vk(pbf_ctx* ctx, size_t n, const U256& omega, const uint64_t* d_q, const uint64_t* d_copies,
-                const uint64_t* d_srs, size_t srs_m, const uint64_t* k1k2, hipStream_t s, uint64_t pre[8][8]);
 // canonical affine (x, y as 4 + 4 little-endian u64; identity (0, 0)) of an XYZZ point
 void xyzz_to_affine_u64(const Xyzz& p, uint64_t* out);
 

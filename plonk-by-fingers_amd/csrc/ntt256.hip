@@ -10,7 +10,7 @@
 #include <type_traits>
 #include <vector>
 #include "../../include/pbf.h"
-#include "fp256.hpp"
+#include "fr_host.hpp"
 #include "fr29.hpp"
 #include "internal.hpp"
 
@@ -471,28 +471,6 @@ static U256 h_from64(const uint64_t* x) {
   for (int i = 0; i < 4; ++i) { r.w[2 * i] = (uint32_t)x[i]; r.w[2 * i + 1] = (uint32_t)(x[i] >> 32); }
   return r;
 }
-static bool h_canonical(const U256& x) { return !Fr::geq_p(x); }
-static U256 h_pow(U256 base_m, uint64_t e) {  // Montgomery in/out
-  U256 r = Fr::to_mont(Fr::one_plain());
-  while (e) {
-    if (e & 1) r = Fr::mul(r, base_m);
-    base_m = Fr::mul(base_m, base_m);
-    e >>= 1;
-  }
-  return r;
-}
-static U256 h_inv(const U256& a_m) {  // a^(r-2), Montgomery
-  // exponent r - 2 as 8 limbs, square-and-multiply from the top
-  uint32_t e[8];
-  for (int i = 0; i < 8; ++i) e[i] = Bn254FrParams::P[i];
-  e[0] -= 2;  // P[0] = 0xf0000001 >= 2
-  U256 r = Fr::to_mont(Fr::one_plain());
-  for (int i = 255; i >= 0; --i) {
-    r = Fr::mul(r, r);
-    if ((e[i / 32] >> (i % 32)) & 1) r = Fr::mul(r, a_m);
-  }
-  return r;
-}
 
 struct Plan256 {
   uint64_t n = 0;
@@ -546,10 +524,10 @@ static int make_plan256(const pbf::Options& o, const uint64_t* omega, uint64_t n
   while ((1ull << log_n) < n) ++log_n;
   if (log_n > 28) return fail(PBF_EINVAL, "n exceeds the 2-adicity of BN254 Fr (2^28)");
   U256 w = h_from64(omega);
-  if (!h_canonical(w)) return fail(PBF_EINVAL, "omega not canonical");
+  if (!fr_canonical(omega)) return fail(PBF_EINVAL, "omega not canonical");
   U256 wm = Fr::to_mont(w);
   const U256 one_m = Fr::to_mont(Fr::one_plain());
-  if (n > 1 && (!Fr::eq(h_pow(wm, n), one_m) || Fr::eq(h_pow(wm, n / 2), one_m)))
+  if (n > 1 && (!Fr::eq(fr_pow(wm, n), one_m) || Fr::eq(fr_pow(wm, n / 2), one_m)))
     return fail(PBF_EINVAL, "omega does not have order n");
   p->n = n; p->log_n = log_n; p->inverse = inverse;
   U256 nm;
@@ -558,9 +536,9 @@ static int make_plan256(const pbf::Options& o, const uint64_t* omega, uint64_t n
     nn.w[0] = (uint32_t)n; nn.w[1] = (uint32_t)(n >> 32);
     nm = Fr::to_mont(nn);
   }
-  p->n_inv = h_inv(nm);
+  p->n_inv = fr_inv(nm);
   if (inverse == 2) p->n_inv = Fr::mul(p->n_inv, Fr::to_mont(Fr::to_mont(Fr::one_plain())));  // n^-1 R
-  if (inverse) wm = h_inv(wm);
+  if (inverse) wm = fr_inv(wm);
   if (n <= 2048) return up256(p->small_tw, h_powers(wm, n));
   // passes of radix <= 2^9 (LDS tile 2048 x 32 B); option ntt256.maxr (4..9) lowers the largest
   // radix (more, lighter passes: every radix family of the planner, tests/test_ntt_fr256_gpu.py)
@@ -576,7 +554,7 @@ static int make_plan256(const pbf::Options& o, const uint64_t* omega, uint64_t n
   // takes one twiddle product, and the pass is linear): tw1s = tw1 n^-1 for the two-level form,
   // the per-pass table scaled likewise.
   {
-    const U256 step = h_pow(wm, 1ull << p->tw_bits);
+    const U256 step = fr_pow(wm, 1ull << p->tw_bits);
     std::vector<U256> t1 = h_powers(step, n >> p->tw_bits);
     rc = up256(p->tw1, t1);
     if (rc) return rc;
@@ -596,7 +574,7 @@ static int make_plan256(const pbf::Options& o, const uint64_t* omega, uint64_t n
     const uint64_t R = 1ull << lr;
     const bool fold = inverse && pi + 1 == p->logr.size();
     auto rb = std::make_shared<DevBuf>();
-    if ((rc = up256(*rb, h_powers(h_pow(wm, n / R), R)))) return rc;
+    if ((rc = up256(*rb, h_powers(fr_pow(wm, n / R), R)))) return rc;
     p->rtab.push_back(rb);
     auto tb = std::make_shared<DevBuf>();
     if (ns > 1 && R * ns > (1ull << 20) && tw_log > 20 && R * ns <= (1ull << tw_log)) {
@@ -609,7 +587,7 @@ static int make_plan256(const pbf::Options& o, const uint64_t* omega, uint64_t n
       const uint64_t step = n / (ns * R);
       std::vector<U256> t(R * ns);
       for (uint64_t r = 0; r < R; ++r) {
-        const U256 wr = h_pow(wm, step * r);
+        const U256 wr = fr_pow(wm, step * r);
         U256 z = one_m;
         for (uint64_t k = 0; k < ns; ++k) { t[r * ns + k] = fold ? Fr::mul(z, p->n_inv) : z; z = Fr::mul(z, wr); }
       }
@@ -856,12 +834,6 @@ static uint32_t grid256(uint64_t count) {
   return (uint32_t)(b > 8192 ? 8192 : (b ? b : 1));
 }
 
-static bool canonical_vec(const uint64_t* v, size_t n) {
-  for (size_t i = 0; i < n; ++i)
-    if (!h_canonical(h_from64(v + 4 * i))) return false;
-  return true;
-}
-
 }  // namespace pbf
 
 using namespace pbf;
@@ -920,7 +892,7 @@ int pbf_ntt_fr256(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* in, uint6
   Plan256* p;
   int rc = get_plan256(ctx, omega, n, inverse, &p);
   if (rc) return rc;
-  if (!canonical_vec(in, n)) return fail(PBF_EINVAL, "input not canonical");
+  if (!fr_canonical(in, n)) return fail(PBF_EINVAL, "input not canonical");
   hipStream_t s = ctx->host_stream();
   if ((rc = ctx->io0.ensure(n * 32))) return rc;
   PBF_HIP(hipMemcpyAsync(ctx->io0.p, in, n * 32, hipMemcpyHostToDevice, s));
@@ -969,7 +941,7 @@ int fr256_scale_pow(bool l29, const uint64_t* in, uint64_t len, uint64_t* out, u
 // to n); inverse: the plain inverse times shift^-j.
 static int fr256_coset_check(const uint64_t* shift, size_t in_len, size_t n, int inverse, U256* sm) {
   const U256 sh = h_from64(shift);
-  if (!h_canonical(sh) || !(shift[0] | shift[1] | shift[2] | shift[3]))
+  if (!fr_canonical(shift) || !(shift[0] | shift[1] | shift[2] | shift[3]))
     return fail(PBF_EINVAL, "shift must be canonical and non-zero");
   if (in_len == 0 || in_len > n) return fail(PBF_EINVAL, "in_len must be in 1..n");
   if (inverse && in_len != n) return fail(PBF_EINVAL, "the inverse coset transform needs in_len == n");
@@ -986,7 +958,7 @@ static int fr256_coset_run(pbf_ctx* ctx, const uint64_t* omega, const U256& sm, 
   const bool l29 = ctx->options.num("ntt256.l29", 1) != 0;
   if (inverse) {
     if ((rc = run256(*p, (const U256*)d_in, (U256*)d_out, batch, ctx->scratch0, ctx->scratch1, s))) return rc;
-    return fr256_scale_pow(l29, d_out, n, d_out, n, batch, h_inv(sm), s);
+    return fr256_scale_pow(l29, d_out, n, d_out, n, batch, fr_inv(sm), s);
   }
   if ((rc = fr256_scale_pow(l29, d_in, in_len, d_out, n, batch, sm, s))) return rc;
   return pbf_internal_ntt_fr256_prefix(ctx, omega, d_out, n, batch, in_len, s);
@@ -1002,7 +974,7 @@ int pbf_ntt_fr256_coset(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* shi
   if (rc) return rc;
   Plan256* p;
   if ((rc = get_plan256(ctx, omega, n, inverse, &p))) return rc;
-  if (!canonical_vec(in, in_len)) return fail(PBF_EINVAL, "input not canonical");
+  if (!fr_canonical(in, in_len)) return fail(PBF_EINVAL, "input not canonical");
   hipStream_t s = ctx->host_stream();
   if ((rc = ctx->io0.ensure(n * 32))) return rc;
   uint64_t* d_out = (uint64_t*)ctx->io0.p;
@@ -1037,7 +1009,7 @@ int pbf_mul_ntt_fr256(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* a, si
   int rc = get_plan256(ctx, omega, n, 0, &fw);
   if (!rc) rc = get_plan256(ctx, omega, n, 1, &iv, true);  // the inverse puts back the product's R
   if (rc) return rc;
-  if (!canonical_vec(a, la) || !canonical_vec(b, lb)) return fail(PBF_EINVAL, "input not canonical");
+  if (!fr_canonical(a, la) || !fr_canonical(b, lb)) return fail(PBF_EINVAL, "input not canonical");
   hipStream_t s = ctx->host_stream();
   if ((rc = ctx->io0.ensure(2 * n * 32))) return rc;
   U256* d = (U256*)ctx->io0.p;
@@ -1108,7 +1080,7 @@ int get_tl256(pbf_ctx* ctx, const U256& wm, uint64_t N, TwoLevel256** out) {
   while ((1ull << log_n) < N) ++log_n;
   t->bits = (log_n + 1) / 2;
   int rc = up256(t->t0, h_powers(wm, 1ull << t->bits));
-  if (!rc) rc = up256(t->t1, h_powers(h_pow(wm, 1ull << t->bits), (N >> t->bits) ? (N >> t->bits) : 1));
+  if (!rc) rc = up256(t->t1, h_powers(fr_pow(wm, 1ull << t->bits), (N >> t->bits) ? (N >> t->bits) : 1));
   if (rc) return rc;
   *out = t.get();
   tl256()[k] = std::move(t);
@@ -1119,11 +1091,11 @@ int shard256_check(const uint64_t* omega, uint32_t G, size_t nl, U256* wm) {
   if (G != 2 && G != 4 && G != 8) return fail(PBF_EINVAL, "world size must be 2, 4 or 8");
   if (nl < G || (nl & (nl - 1))) return fail(PBF_EINVAL, "per-rank size must be a power of two >= G");
   const U256 w = h_from64(omega);
-  if (!h_canonical(w)) return fail(PBF_EINVAL, "omega not canonical");
+  if (!fr_canonical(omega)) return fail(PBF_EINVAL, "omega not canonical");
   *wm = Fr::to_mont(w);
   const uint64_t N = (uint64_t)G * nl;
   const U256 one_m = Fr::to_mont(Fr::one_plain());
-  if (!Fr::eq(h_pow(*wm, N), one_m) || Fr::eq(h_pow(*wm, N / 2), one_m))
+  if (!Fr::eq(fr_pow(*wm, N), one_m) || Fr::eq(fr_pow(*wm, N / 2), one_m))
     return fail(PBF_EINVAL, "omega does not have order G*nl");
   return 0;
 }
@@ -1148,7 +1120,7 @@ int pbf_ntt_fr256_shard_local_dev(pbf_ctx* ctx, const uint64_t* omega, uint32_t 
   if (rc) return rc;
   PBF_HIP(hipSetDevice(ctx->device));
   uint64_t wl[4];
-  u256_to_u64(Fr::from_mont(h_pow(wm, world)), wl);  // local root w^G, order nl
+  u256_to_u64(Fr::from_mont(fr_pow(wm, world)), wl);  // local root w^G, order nl
   Plan256* p;
   if ((rc = get_plan256(ctx, wl, nl, inverse, &p))) return rc;
   hipStream_t s = (hipStream_t)stream;
@@ -1181,7 +1153,7 @@ int pbf_ntt_fr256_shard_combine_dev(pbf_ctx* ctx, const uint64_t* omega, uint32_
   if (rank >= world) return fail(PBF_EINVAL, "rank out of range");
   PBF_HIP(hipSetDevice(ctx->device));
   const uint64_t N = (uint64_t)world * nl;
-  const U256 root = inverse ? h_inv(wm) : wm;
+  const U256 root = inverse ? fr_inv(wm) : wm;
   TwoLevel256* tl;
   if ((rc = get_tl256(ctx, root, N, &tl))) return rc;
   Shard256Args a;
@@ -1195,7 +1167,7 @@ int pbf_ntt_fr256_shard_combine_dev(pbf_ctx* ctx, const uint64_t* omega, uint32_
   a.rank = rank;
   a.n_mask = N - 1;
   a.batch = batch;
-  const U256 wG = h_pow(root, nl);  // primitive G-th root (direction-specific)
+  const U256 wG = fr_pow(root, nl);  // primitive G-th root (direction-specific)
   U256 x = Fr::to_mont(Fr::one_plain());
   for (uint32_t i = 0; i < 8; ++i) {
     a.wg[i] = x;
@@ -1204,7 +1176,7 @@ int pbf_ntt_fr256_shard_combine_dev(pbf_ctx* ctx, const uint64_t* omega, uint32_
   {
     U256 gg = Fr::one_plain();
     gg.w[0] = world;
-    a.scale = inverse ? h_inv(Fr::to_mont(gg)) : Fr::to_mont(Fr::one_plain());
+    a.scale = inverse ? fr_inv(Fr::to_mont(gg)) : Fr::to_mont(Fr::one_plain());
   }
   void (*fn)(Shard256Args) = nullptr;
   switch (world) {

@@ -11,8 +11,8 @@
 //        3n+6 .. 4n-1 of t are zero" (also the 3-way split's precondition, plonk.rs:376-378
 //        generalised to n+2 coefficients per part)
 //   evaluations at z (Poly::eval, plonk.rs:393-399)              -> chunked Horner + reduction
-//   W_z, W_zw (Poly::div by x - z, plonk.rs:430-442)             -> pointwise on the coset
-//        (the numerators vanish at z exactly) + coset INTT
+//   W_z, W_zw (Poly::div by x - z, plonk.rs:430-442)             -> blocked synthetic division
+//        on the coefficients (k_hs1..3); the remainder must be zero
 //   SRS::eval_at_s commitments (plonk.rs:51-58)                 -> Pippenger MSM (msm.hip)
 //
 // Every output is the unique mathematical value the reference's formulas define (the
@@ -23,14 +23,19 @@
 //
 // Field elements at rest in HBM: canonical Fr, 4 x u64 little-endian (the ABI layout);
 // kernels convert to Montgomery on load and back on store.
+//
+// Layout: the Fr polynomial kernels and their launchers (prover.hpp exports the ones kzg.hip and
+// verify.hip share), the Prover helper struct, then Plonk::prove as prove_setup and its two
+// siblings prove_single and prove_sharded, which take the protocol's scalar terms from
+// plonk_terms.hpp; the synthetic circuit and the SRS at the end. The verifier is verify.hip.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <ctime>
 #include <vector>
 #include "../../include/pbf.h"
-#include "msm.hpp"
-#include "kzg.hpp"
+#include "prover.hpp"
+#include "plonk_terms.hpp"
 #include "fr29.hpp"
 
 // ntt256.hip: the coset transforms' batched forward NTT of zero-padded prefixes
@@ -39,31 +44,8 @@ int pbf_internal_ntt_fr256_prefix(pbf_ctx* ctx, const uint64_t* omega, uint64_t*
 
 namespace pbf {
 
-typedef uint64_t fr4[4];
-
 __device__ __forceinline__ U256 ldr(const uint64_t* p) { return Fr::to_mont(u256_from_u64(p)); }
 __device__ __forceinline__ void str(uint64_t* p, const U256& m) { u256_to_u64(Fr::from_mont(m), p); }
-__host__ __device__ __forceinline__ U256 fr_one_m() { return Fr::to_mont(Fr::one_plain()); }
-
-__device__ U256 fr_pow(U256 a, uint64_t e) {
-  U256 r = fr_one_m();
-  while (e) {
-    if (e & 1) r = Fr::mul(r, a);
-    a = Fr::mul(a, a);
-    e >>= 1;
-  }
-  return r;
-}
-// a^(r-2): Fermat inverse (a != 0)
-__device__ U256 fr_inv(const U256& a) {
-  U256 r = fr_one_m();
-  for (int i = 255; i >= 0; --i) {
-    r = Fr::mul(r, r);
-    uint32_t e = Bn254FrParams::P[i / 32] - (i < 32 ? 2u : 0u);
-    if ((e >> (i % 32)) & 1) r = Fr::mul(r, a);
-  }
-  return r;
-}
 
 constexpr int PV_CHUNK = 32;  // elements per thread in the chunked kernels
 
@@ -86,8 +68,8 @@ __device__ __forceinline__ U256 pow64(U256 b) {
 // (coset scaling with zero padding; with in_stride = e_mult = G, in_off = e_off = rank it
 // extracts rank's stride shard of the scaled vector). The product of a canonical value and
 // a Montgomery-form power is the canonical product (a * xR * R^-1): no conversions.
-// c0 (Montgomery form, used when has_c0): an extra constant factor of every output -- the
-// quotient's circuit slots come out at a chosen R-degree this way, for free (see QuotArgs)
+// c0 (Montgomery form, folded into x0 by the host): an extra constant factor of every output --
+// the quotient's circuit slots come out at a chosen R-degree this way, for free (see QuotArgs)
 // Round 4: a thread's first power c0 base^(e_off + e_mult i0), i0 = 64 PV_CHUNK v + l (wave v,
 // lane l), comes from host-computed tables instead of two square-and-multiply chains per thread
 // (~80 dependent products, which were most of the kernel's time at 2^20 gates): x0 = c0
@@ -138,22 +120,15 @@ __device__ __forceinline__ U256 blk_next_x(const Blk& b, uint64_t p, const U256&
   return Fr::mul_tp(g, fr_pow(w, blk_index(b, p + 64)));
 }
 
-// host Montgomery power a^e (a in Montgomery form)
-static U256 h_pow(U256 a, uint64_t e) {
-  U256 r = fr_one_m();
-  for (; e; e >>= 1, a = Fr::mul(a, a))
-    if (e & 1) r = Fr::mul(r, a);
-  return r;
-}
 // the start-power tables of x0 base^(e_off + e_mult i) (k_scale_pow, k_powers29), host products
 static ScalePow scale_pow_tab(const U256& x0, const U256& base, uint64_t e_off, uint64_t e_mult) {
   ScalePow sp;
-  sp.x0 = Fr::mul(x0, h_pow(base, e_off));
-  sp.step = h_pow(base, 64 * e_mult);
-  const U256 bm = h_pow(base, e_mult);
+  sp.x0 = Fr::mul(x0, fr_pow(base, e_off));
+  sp.step = fr_pow(base, 64 * e_mult);
+  const U256 bm = fr_pow(base, e_mult);
   sp.tl[0] = fr_one_m();
   for (int l = 1; l < 64; ++l) sp.tl[l] = Fr::mul(sp.tl[l - 1], bm);
-  sp.tv[0] = h_pow(sp.step, PV_CHUNK);
+  sp.tv[0] = fr_pow(sp.step, PV_CHUNK);
   for (int k = 1; k < SP_WBITS; ++k) sp.tv[k] = Fr::mul(sp.tv[k - 1], sp.tv[k - 1]);
   return sp;
 }
@@ -670,7 +645,7 @@ static void launch_quotient(const QuotArgs& qa, uint64_t* out, bool l29, hipStre
 // consecutive k runs its recurrence from 0 (per thread, then a Hillis-Steele pass over the
 // threads with multipliers z^(HS_PER 2^j)) and leaves its total; (2) one block turns the
 // totals into each block's incoming s (multiplier z^HS_BLK); (3) s_k += z^(k - k_b + 1) s_in.
-// (HS_T, HS_PER, HS_BLK, HS_LOG_T and HsArgs: kzg.hpp, shared with the KZG opening)
+// (HS_T, HS_PER, HS_BLK, HS_LOG_T and HsArgs: prover.hpp, shared with the KZG opening)
 // q[L-2-k] <- block-local s_k (k < L-1); the block-local remainder candidate in rem[block]
 // (v[] lives in scratch here (528 B per lane); compile-time indices keep it in 213 VGPRs at two
 // waves per SIMD, which measured 4 % slower: 1.74 against 1.68 ms for the two 2^24 divisions)
@@ -955,8 +930,8 @@ static int launch_eval(EvalArgs& e, int np, DevBuf& partial, uint64_t* evals, hi
     if (j == nx) {
       if (nx == EV_XS) return fail(PBF_EINVAL, "more distinct evaluation points than power tables");
       kx[j] = e.x[p]; koff[j] = e.off[p];
-      e.xoff[j] = h_pow(e.x[p], e.off[p]);
-      e.pw[j][0] = h_pow(e.x[p], EV_PER);
+      e.xoff[j] = fr_pow(e.x[p], e.off[p]);
+      e.pw[j][0] = fr_pow(e.x[p], EV_PER);
       for (int k = 1; k < EV_PW; ++k) e.pw[j][k] = Fr::mul(e.pw[j][k - 1], e.pw[j][k - 1]);
       ++nx;
     }
@@ -971,50 +946,6 @@ static int launch_eval(EvalArgs& e, int np, DevBuf& partial, uint64_t* evals, hi
   return 0;
 }
 
-// ---------------------------------------------------------------- host helpers
-static U256 hm(const uint64_t* p) { return Fr::to_mont(u256_from_u64(p)); }
-static U256 hm64(uint64_t v) {
-  U256 r = u256_zero();
-  r.w[0] = (uint32_t)v;
-  r.w[1] = (uint32_t)(v >> 32);
-  return Fr::to_mont(r);
-}
-static U256 hpowm(U256 a, const U256& e_plain) {  // exponent given as plain U256
-  U256 r = fr_one_m();
-  for (int i = 255; i >= 0; --i) {
-    r = Fr::mul(r, r);
-    if ((e_plain.w[i / 32] >> (i % 32)) & 1) r = Fr::mul(r, a);
-  }
-  return r;
-}
-static U256 hpow64(U256 a, uint64_t e) {
-  U256 r = fr_one_m();
-  while (e) {
-    if (e & 1) r = Fr::mul(r, a);
-    a = Fr::mul(a, a);
-    e >>= 1;
-  }
-  return r;
-}
-static U256 hinvm(const U256& a) {
-  U256 e;
-  for (int i = 0; i < 8; ++i) e.w[i] = Bn254FrParams::P[i];
-  e.w[0] -= 2;
-  return hpowm(a, e);
-}
-static void hout(uint64_t* p, const U256& m) { u256_to_u64(Fr::from_mont(m), p); }
-static bool heq1(const U256& m) { return Fr::eq(m, fr_one_m()); }
-// primitive 2^k-th root of unity of Fr: 5^((r-1)/2^k)
-static U256 hroot(uint32_t log_n) {
-  U256 e;  // (r-1) >> log_n
-  for (int i = 0; i < 8; ++i) e.w[i] = Bn254FrParams::P[i];
-  e.w[0] -= 1;
-  for (uint32_t s = 0; s < log_n; ++s) {
-    for (int i = 0; i < 8; ++i) e.w[i] = (e.w[i] >> 1) | (i < 7 ? (e.w[i + 1] << 31) : 0);
-  }
-  return hpowm(hm64(5), e);
-}
-
 struct ProverBufs {
   DevBuf &hpow, &sigma, &coef, &acc, &tmp0, &tmp1, &tmp2, &coset, &t, &work, &flag, &evals, &partial;
   explicit ProverBufs(pbf_ctx* c)
@@ -1024,11 +955,11 @@ struct ProverBufs {
         partial(c->buf("pv.partial")) {}
 };
 
-// ---------------------------------------------------------------- kzg.hpp: the launchers shared
-// with the KZG entry points
+// ---------------------------------------------------------------- prover.hpp: the launchers shared
+// with the KZG entry points and the verifiers
 void hs_set_point(HsArgs& a, const U256& z) {
   a.z = z;
-  for (int j = 0; j < HS_LOG_T; ++j) a.zs[j] = hpow64(z, (uint64_t)HS_PER << j);
+  for (int j = 0; j < HS_LOG_T; ++j) a.zs[j] = fr_pow(z, (uint64_t)HS_PER << j);
 }
 int hs_div_run(pbf_ctx* ctx, const HsArgs& a, uint64_t* q, uint64_t* rem, hipStream_t s) {
   const uint64_t nb = (a.L + HS_BLK - 1) / HS_BLK;
@@ -1037,22 +968,22 @@ int hs_div_run(pbf_ctx* ctx, const HsArgs& a, uint64_t* q, uint64_t* rem, hipStr
   if (rc) return rc;
   uint64_t* totals = (uint64_t*)hb.p;
   hipLaunchKernelGGL(k_hs1, dim3((uint32_t)nb), dim3(HS_T), 0, s, a, q, totals, rem);
-  const U256 zb = hpow64(a.z, HS_BLK);
-  hipLaunchKernelGGL(k_hs2, dim3(1), dim3(HS_T), 0, s, totals, nb, zb, hpow64(zb, (nb + HS_T - 1) / HS_T));
+  const U256 zb = fr_pow(a.z, HS_BLK);
+  hipLaunchKernelGGL(k_hs2, dim3(1), dim3(HS_T), 0, s, totals, nb, zb, fr_pow(zb, (nb + HS_T - 1) / HS_T));
   hipLaunchKernelGGL(k_hs3, dim3((uint32_t)nb), dim3(HS_T), 0, s, q, a.L, a, (const uint64_t*)totals, rem);
   PBF_HIP(hipGetLastError());
   return 0;
 }
-int fr_eval_run(const uint64_t* const* polys, const uint64_t* lens, const U256* xs, int np, DevBuf& partial,
-                uint64_t* d_evals, hipStream_t s) {
+int fr_eval_run(const uint64_t* const* polys, const uint64_t* lens, const U256* xs, int np, uint64_t off,
+                DevBuf& partial, uint64_t* d_evals, hipStream_t s) {
   if (np < 1 || np > 12) return fail(PBF_EINVAL, "1 .. 12 polynomials per evaluation launch");
   EvalArgs e;
-  uint64_t longest = 0;
+  uint64_t longest = 1;  // one chunk at least: a rank may hold no coefficient of any polynomial
   for (int p = 0; p < np; ++p) {
     e.poly[p] = polys[p];
     e.len[p] = lens[p];
     e.x[p] = xs[p];
-    e.off[p] = 0;
+    e.off[p] = off;
     longest = std::max(longest, lens[p]);
   }
   e.chunks = (longest + (uint64_t)EV_T * EV_PER - 1) / ((uint64_t)EV_T * EV_PER);
@@ -1061,17 +992,27 @@ int fr_eval_run(const uint64_t* const* polys, const uint64_t* lens, const U256* 
   PBF_HIP(hipGetLastError());
   return 0;
 }
-int fr_lincomb_run(const uint64_t* const* in, const U256* c, int k, uint64_t len, uint64_t* out, hipStream_t s) {
+int fr_lincomb_run(int k, const uint64_t* const* in, const uint64_t* lens, const U256* c, const U256& c0,
+                   uint64_t* out, uint64_t count, hipStream_t s) {
   if (k < 1 || k > 10) return fail(PBF_EINVAL, "1 .. 10 inputs per linear combination");
   LinComb L;
   for (int i = 0; i < k; ++i) {
     L.in[i] = in[i];
-    L.len[i] = len;
+    L.len[i] = lens[i];
     L.c[i] = c[i];
   }
   L.k = k;
-  L.c0 = u256_zero();
-  hipLaunchKernelGGL(k_lincomb, dim3(blocks_for(len)), dim3(256), 0, s, L, out, len);
+  L.c0 = c0;
+  hipLaunchKernelGGL(k_lincomb, dim3(blocks_for(count)), dim3(256), 0, s, L, out, count);
+  PBF_HIP(hipGetLastError());
+  return 0;
+}
+int sigma_table_run(uint64_t n, const U256& omega, const U256& k1, const U256& k2, const uint64_t* d_copies,
+                    uint64_t* hpow, uint64_t* sigma, int* bad, hipStream_t s) {
+  hipLaunchKernelGGL(k_powers29, dim3(blocks_for((n + PV_CHUNK - 1) / PV_CHUNK)), dim3(256), 0, s, hpow, n,
+                     powers_tab29(omega, fr_one_m()));
+  hipLaunchKernelGGL(k_sigma, dim3(blocks_for(3 * n)), dim3(256), 0, s, d_copies, (const uint64_t*)hpow, n, (uint64_t)0,
+                     n, k1, k2, sigma, bad);
   PBF_HIP(hipGetLastError());
   return 0;
 }
@@ -1086,13 +1027,12 @@ struct Prover {
   pbf_ctx* ctx;
   hipStream_t s;
   uint64_t n, N;
-  uint32_t log_n;
-  U256 omega, omegaN, omegaN_inv, g, g_inv;
+  U256 omega, omegaN, g, g_inv;
   uint64_t w_plain[4], wN_plain[4];
   int* d_bad;
   bool timing = false;
   double t_last = 0;
-  // PBF_PROVER_TIMING=1: per-round wall times on stderr (stream synchronised at each mark)
+  // option prover.timing = 1: per-round wall times on stderr (stream synchronised at each mark)
   void mark(const char* what) {
     if (!timing) return;
     (void)hipStreamSynchronize(s);
@@ -1146,36 +1086,20 @@ struct Prover {
       hipLaunchKernelGGL(k_scale_pow, dim3(blocks_for((cnt + PV_CHUNK - 1) / PV_CHUNK)), dim3(256), 0, s, in, in_off,
                          in_stride, len, out, cnt, sp);
   }
-  // k coset NTTs of size N: slot i = evaluations of sum_j srcs[i][j] (bases[i] x)^j at g w_N^e
-  // (this rank's blocks when sharded), slots count() apart in `out`, at R-degree degs[i]
-  // (null: canonical)
+  // k coset NTTs of size N on one GPU: slot i = evaluations of sum_j srcs[i][j] (bases[i] x)^j at
+  // g w_N^e, slots N apart in `out`, at R-degree degs[i] (null: canonical). Sharded: coset_ntt_ss.
   int coset_ntt_batch(int k, const uint64_t* const* srcs, const uint64_t* lens, const U256* bases, uint64_t* out,
                       const int* degs = nullptr) {
-    if (G == 1) {
-      // only the scaled coefficients are written (the longest length of the batch; round 6): the
-      // transform's first pass reads nothing past them (pbf_internal_ntt_fr256_prefix), so the
-      // 3/4 of every 4n slot that is zero padding is neither stored nor loaded
-      uint64_t mx = 0;
-      for (int i = 0; i < k; ++i) mx = lens[i] > mx ? lens[i] : mx;
-      if (mx > N) mx = N;
-      for (int i = 0; i < k; ++i)
-        scale(srcs[i], 0, 1, lens[i], out + 4 * N * i, mx, bases[i], 0, 1, degs ? degs[i] : 0);
-      PBF_HIP(hipGetLastError());
-      return pbf_internal_ntt_fr256_prefix(ctx, wN_plain, out, N, k, mx, s);  // one batched NTT
-    }
-    uint64_t* sh = (uint64_t*)shard->p;
+    // only the scaled coefficients are written (the longest length of the batch; round 6): the
+    // transform's first pass reads nothing past them (pbf_internal_ntt_fr256_prefix), so the
+    // 3/4 of every 4n slot that is zero padding is neither stored nor loaded
+    uint64_t mx = 0;
+    for (int i = 0; i < k; ++i) mx = lens[i] > mx ? lens[i] : mx;
+    if (mx > N) mx = N;
     for (int i = 0; i < k; ++i)
-      scale(srcs[i], rank, G, lens[i], sh + 4 * nl * i, nl, bases[i], rank, G, degs ? degs[i] : 0);
+      scale(srcs[i], 0, 1, lens[i], out + 4 * N * i, mx, bases[i], 0, 1, degs ? degs[i] : 0);
     PBF_HIP(hipGetLastError());
-    return sharded_ntt_from_staging(k, out);
-  }
-  // the sharded forward NTT of the k stride shards in the staging buffer into this rank's blocks
-  int sharded_ntt_from_staging(int k, uint64_t* out) {
-    uint64_t* sh = (uint64_t*)shard->p;
-    int rc = pbf_ntt_fr256_shard_local_dev(ctx, wN_plain, G, sh, (uint64_t*)comm->send, nl, k, 0, s);
-    if (!rc) rc = a2a((size_t)k * S * 32);
-    if (!rc) rc = pbf_ntt_fr256_shard_combine_dev(ctx, wN_plain, G, rank, (const uint64_t*)comm->recv, out, nl, k, 0, s);
-    return rc;
+    return pbf_internal_ntt_fr256_prefix(ctx, wN_plain, out, N, k, mx, s);  // one batched NTT
   }
   // coefficients of the polynomial whose N coset evaluations are `ev` (one GPU)
   int coset_intt(uint64_t* ev, uint64_t* out) {
@@ -1287,7 +1211,11 @@ struct Prover {
     for (int i = 0; i < k; ++i)
       scale(ss[i], 0, 1, ss_count(lens[i]), sh + 4 * nl * i, nl, bases[i], rank, G, degs ? degs[i] : 0);
     PBF_HIP(hipGetLastError());
-    return sharded_ntt_from_staging(k, out);
+    // the sharded forward NTT of the k stride shards in the staging buffer into this rank's blocks
+    int rc = pbf_ntt_fr256_shard_local_dev(ctx, wN_plain, G, sh, (uint64_t*)comm->send, nl, k, 0, s);
+    if (!rc) rc = a2a((size_t)k * S * 32);
+    if (!rc) rc = pbf_ntt_fr256_shard_combine_dev(ctx, wN_plain, G, rank, (const uint64_t*)comm->recv, out, nl, k, 0, s);
+    return rc;
   }
   // the SS coefficients (nl slots, j = rank + G m < N) of the polynomial whose coset
   // evaluations are this rank's blocks `ev`
@@ -1334,8 +1262,8 @@ struct Prover {
     const uint64_t hi = crlo() + cnt;
     for (uint32_t g = 0; g < G; ++g) {
       const uint64_t lo_g = (uint64_t)g * Bc;
-      value = Fr::add(value, Fr::mul(T[g], hpow64(z, lo_g)));
-      if (g > rank) V = Fr::add(V, Fr::mul(T[g], hpow64(z, lo_g - hi)));  // nonzero only above a full range
+      value = Fr::add(value, Fr::mul(T[g], fr_pow(z, lo_g)));
+      if (g > rank) V = Fr::add(V, Fr::mul(T[g], fr_pow(z, lo_g - hi)));  // nonzero only above a full range
     }
     if (!Fr::is_zero(Fr::sub(value, y))) return fail(PBF_EINVAL, err);
     if (cnt)
@@ -1374,6 +1302,85 @@ struct Prover {
   }
 };
 
+// What prove_setup leaves for prove_single / prove_sharded: the validated inputs in Montgomery
+// form, the initialised Prover, the scratch buffers and the slot tables.
+struct ProveState {
+  Prover P;
+  ProverBufs B;  // context-owned scratch (one ctx per host thread, pbf.h)
+  int mode = 0;
+  const uint64_t *d_q = nullptr, *d_copies = nullptr, *d_abc = nullptr;
+  PlonkChallenges ch;
+  U256 bl[9];  // the blinders b1..b9
+  // proving key: on (option prover.pk), found valid in the context, and the key to store once built
+  bool pk_on = false, pk_hit = false;
+  std::vector<uint64_t> pk_key;
+  uint64_t* pkcoef = nullptr;
+  // coefficient slots: 0 a, 1 b, 2 c, 3 q_l, 4 q_r, 5 q_o, 6 q_m, 7 q_c, 8 s1, 9 s2, 10 s3 (3.. in
+  // the proving key); coset slots: 0 a 1 b 2 c 3 z 4 ql 5 qr 6 qo 7 qm 8 qc 9 s1 10 s2 11 s3 12 l1
+  // [13 z(w x), sharded]
+  uint64_t *cslot[11], *ceslot[14];
+  uint64_t *out_pts = nullptr, *out_f = nullptr;
+  explicit ProveState(pbf_ctx* ctx) : B(ctx) {}
+};
+
+// a(x) = (b2 + b1 x)(x^n - 1) + f_a(x), likewise b, c (plonk.rs:250-252): lo = b2, hi = b1
+Blind blind_abc(uint64_t n, const U256& lo, const U256& hi) {
+  Blind b;
+  b.count = 4;
+  b.idx[0] = 0; b.delta[0] = Fr::sub(u256_zero(), lo);
+  b.idx[1] = 1; b.delta[1] = Fr::sub(u256_zero(), hi);
+  b.idx[2] = n; b.delta[2] = lo;
+  b.idx[3] = n + 1; b.delta[3] = hi;
+  return b;
+}
+// z(x) = (b9 + b8 x + b7 x^2)(x^n - 1) + acc(x)   (plonk.rs:309)
+Blind blind_z(uint64_t n, const U256* bl) {
+  Blind b;
+  b.count = 6;
+  const U256 c0 = bl[8], c1 = bl[7], c2 = bl[6];
+  b.idx[0] = 0; b.delta[0] = Fr::sub(u256_zero(), c0);
+  b.idx[1] = 1; b.delta[1] = Fr::sub(u256_zero(), c1);
+  b.idx[2] = 2; b.delta[2] = Fr::sub(u256_zero(), c2);
+  b.idx[3] = n; b.delta[3] = c0;
+  b.idx[4] = n + 1; b.delta[4] = c1;
+  b.idx[5] = n + 2; b.delta[5] = c2;
+  return b;
+}
+// the quotient kernel's arguments over the coset slots CE(0..12) and z(w x) at `zw` (null: read
+// from z at index i + 4), with the constants at the R-degrees the quotient's terms need
+// (QuotArgs): Montgomery form is degree 1
+int quot_args(const ProveState& S, const uint64_t* zw, QuotArgs& qa) {
+  const Prover& P = S.P;
+  uint64_t* const* CE = S.ceslot;
+  qa.a = CE[0]; qa.b = CE[1]; qa.c = CE[2]; qa.z = CE[3]; qa.ql = CE[4]; qa.qr = CE[5]; qa.qo = CE[6];
+  qa.qm = CE[7]; qa.qc = CE[8]; qa.s1 = CE[9]; qa.s2 = CE[10]; qa.s3 = CE[11]; qa.l1 = CE[12];
+  qa.zw = zw;
+  qa.N = P.count();
+  qa.N_all = P.N;
+  qa.blk = P.blk();
+  qa.beta0 = Fr::from_mont(S.ch.beta);
+  qa.gamma0 = Fr::from_mont(S.ch.gamma);
+  qa.alpha4 = Fr::to_mont(Fr::to_mont(Fr::to_mont(S.ch.alpha)));
+  qa.k1 = S.ch.k1; qa.k2 = S.ch.k2;
+  qa.alpha2 = Fr::mul(S.ch.alpha, S.ch.alpha);
+  qa.g = P.g; qa.wN = P.omegaN;
+  // Z_H(g w_N^i) = g^n w_4^(i mod 4) - 1
+  const U256 w4 = fr_pow(P.omegaN, P.n);
+  U256 x = fr_pow(P.g, P.n);
+  for (int j = 0; j < 4; ++j) {
+    const U256 d = Fr::sub(x, fr_one_m());
+    if (Fr::is_zero(d)) return fail(PBF_EINVAL, "coset meets H");
+    qa.zh_inv[j] = fr_inv(d);
+    x = Fr::mul(x, w4);
+  }
+  return 0;
+}
+// a_z b_z c_z s1_z s2_z r_z zw_z, canonical: the proof's field elements
+void write_proof_fields(uint64_t* out_f, const PlonkEvals& e) {
+  const U256 fo[7] = {e.a_z, e.b_z, e.c_z, e.s1_z, e.s2_z, e.r_z, e.zw_z};
+  for (int i = 0; i < 7; ++i) hout(out_f + 4 * i, fo[i]);
+}
+
 }  // namespace
 
 // ---- Plonk::prove across G ranks (pbf_plonk_prove_bn254_sharded_dev). Every
@@ -1384,18 +1391,19 @@ struct Prover {
 // all-gathers of a few field elements (flags, scan totals, evaluation partials, division
 // totals) and of the commitments' partial sums. The proving key (circuit polynomials) is built
 // once per circuit with full-length coefficient slots on every rank and this rank's coset blocks.
-static int prove_sharded(Prover& P, ProverBufs& B, int mode, bool pk_on, bool pk_hit, const std::vector<uint64_t>& pk_key,
-                         uint64_t* const* cslot, uint64_t* const* ceslot, const uint64_t* d_q, const uint64_t* d_copies,
-                         const uint64_t* d_abc, const U256& k1, const U256& k2, const U256* bl, const U256& alpha,
-                         const U256& beta, const U256& gamma, const U256& zc, const U256& v, uint64_t* out_pts,
-                         uint64_t* out_f) {
+static int prove_sharded(ProveState& S) {
+  Prover& P = S.P;
+  ProverBufs& B = S.B;
   pbf_ctx* ctx = P.ctx;
   const hipStream_t s = P.s;
+  const int mode = S.mode;
+  const uint64_t *d_q = S.d_q, *d_copies = S.d_copies, *d_abc = S.d_abc;
+  const U256 &k1 = S.ch.k1, &k2 = S.ch.k2, &beta = S.ch.beta, &gamma = S.ch.gamma, &zc = S.ch.z;
   const uint64_t n = P.n, G = P.G, r = P.rank, Bn = P.B, Sn = Bn / G, NE = P.nl;
   const uint64_t E = 32, CRS = P.CRS(), SSS = P.SSS();
   const U256 one = fr_one_m();
-  auto C = [&](int k) { return cslot[k]; };
-  auto CE = [&](int k) { return ceslot[k]; };
+  auto C = [&](int k) { return S.cslot[k]; };
+  auto CE = [&](int k) { return S.ceslot[k]; };
   int rc;
   // ---- this rank's pieces
   DevBuf& shb = ctx->buf("pv.sh");
@@ -1433,12 +1441,12 @@ static int prove_sharded(Prover& P, ProverBufs& B, int mode, bool pk_on, bool pk
   // ---- h = w^i (all of H: copy labels point anywhere)
   hipLaunchKernelGGL(k_powers29, dim3(blocks_for((n + PV_CHUNK - 1) / PV_CHUNK)), dim3(256), 0, s, hpow, n, powers_tab29(P.omega, one));
   PBF_HIP(hipGetLastError());
-  const U256 ninv = hinvm(hm64(n));
+  const U256 ninv = fr_inv(hm64(n));
   // ---- proving key, sharded like the witness (once per circuit; every proof without the key):
   // the 8 circuit polynomials by one sharded INTT of their blocked evaluations (q columns, sigma
   // labels of the blocked rows), their coset blocks from the SS coefficients, their CR ranges by
   // transposes; l1 = n^-1 (1 + x + ... + x^(n-1)) is n^-1 in every slot of both layouts
-  if (!pk_hit) {
+  if (!S.pk_hit) {
     DevBuf& pkb = ctx->buf("pv.pkb");
     if ((rc = pkb.ensure(2 * 8 * Bn * E))) return rc;
     uint64_t* Xk = (uint64_t*)pkb.p;
@@ -1474,7 +1482,7 @@ static int prove_sharded(Prover& P, ProverBufs& B, int mode, bool pk_on, bool pk
       if ((rc = P.xpose(np, ss, Bn, off, len, cr))) return rc;
     }
     pkb.release();
-    if (pk_on) ctx->pk_key = pk_key;
+    if (S.pk_on) ctx->pk_key = S.pk_key;
   }
   {  // l1's CR range: n^-1 for j < n
     PBF_HIP(hipMemsetAsync(l1, 0, CRS * E, s));
@@ -1484,7 +1492,7 @@ static int prove_sharded(Prover& P, ProverBufs& B, int mode, bool pk_on, bool pk
                          powers_tab29(one, ninv));
     PBF_HIP(hipGetLastError());
   }
-  P.mark(pk_hit ? "proving key (cached)" : "proving key (built)");
+  P.mark(S.pk_hit ? "proving key (cached)" : "proving key (built)");
 
   // ---- round 1: interpolate_at_h of a b c (plonk.rs:233-243) = one sharded INTT of their
   // blocked evaluations: blocked slot q Sn + kk <- row q B + r Sn + kk of every column
@@ -1497,16 +1505,9 @@ static int prove_sharded(Prover& P, ProverBufs& B, int mode, bool pk_on, bool pk
   PBF_HIP(hipMemsetAsync(abc_ss, 0, 3 * SSS * E, s));
   PBF_HIP(hipMemcpy2DAsync(abc_ss, SSS * E, X, Bn * E, Bn * E, 3, hipMemcpyDeviceToDevice, s));
   // a(x) = (b2 + b1 x)(x^n - 1) + f_a(x), likewise b, c (plonk.rs:250-252), on the SS pieces
-  for (int k = 0; k < 3; ++k) {
-    const U256 lo = bl[2 * k + 1], hi = bl[2 * k];
-    Blind b;
-    b.count = 4;
-    b.idx[0] = 0; b.delta[0] = Fr::sub(u256_zero(), lo);
-    b.idx[1] = 1; b.delta[1] = Fr::sub(u256_zero(), hi);
-    b.idx[2] = n; b.delta[2] = lo;
-    b.idx[3] = n + 1; b.delta[3] = hi;
-    hipLaunchKernelGGL(k_blind_map, dim3(1), dim3(64), 0, s, abc_ss + 4 * SSS * k, P.bmap(b, true));
-  }
+  for (int k = 0; k < 3; ++k)
+    hipLaunchKernelGGL(k_blind_map, dim3(1), dim3(64), 0, s, abc_ss + 4 * SSS * k,
+                       P.bmap(blind_abc(n, S.bl[2 * k + 1], S.bl[2 * k]), true));
   PBF_HIP(hipGetLastError());
   {
     const uint64_t* ss[3] = {abc_ss, abc_ss + 4 * SSS, abc_ss + 8 * SSS};
@@ -1548,12 +1549,8 @@ static int prove_sharded(Prover& P, ProverBufs& B, int mode, bool pk_on, bool pk
     for (uint64_t g = 0; g < r; ++g) Ep = Fr::mul(Ep, T[g]);
     // acc rows times Ep, straight into the all-to-all's send buffer: rows [r B, (r + 1) B) in
     // order are the [dst][Sn] send layout that lands as the blocked layout of the INTT below
-    LinComb L;
-    L.k = 1;
-    L.in[0] = accr; L.len[0] = Bn; L.c[0] = Ep;
-    L.c0 = u256_zero();
-    hipLaunchKernelGGL(k_lincomb, dim3(blocks_for(Bn)), dim3(256), 0, s, L, send, Bn);
-    PBF_HIP(hipGetLastError());
+    const uint64_t* in[1] = {accr};
+    if ((rc = fr_lincomb_run(1, in, &Bn, &Ep, u256_zero(), send, Bn, s))) return rc;
   }
   if ((rc = P.a2a(Sn * E))) return rc;  // recv: this rank's blocked rows
   if ((rc = pbf_ntt_fr256_shard_combine_dev(ctx, P.w_plain, (uint32_t)G, (uint32_t)r, recv, send, Bn, 1, 1, s))) return rc;
@@ -1561,19 +1558,8 @@ static int prove_sharded(Prover& P, ProverBufs& B, int mode, bool pk_on, bool pk
   if ((rc = pbf_ntt_fr256_shard_local_dev(ctx, P.w_plain, (uint32_t)G, recv, X, Bn, 1, 1, s))) return rc;
   PBF_HIP(hipMemsetAsync(z_ss, 0, SSS * E, s));
   PBF_HIP(hipMemcpyAsync(z_ss, X, Bn * E, hipMemcpyDeviceToDevice, s));
-  {
-    Blind b;  // z(x) = (b9 + b8 x + b7 x^2)(x^n - 1) + acc(x)   (plonk.rs:309)
-    b.count = 6;
-    const U256 c0 = bl[8], c1 = bl[7], c2 = bl[6];
-    b.idx[0] = 0; b.delta[0] = Fr::sub(u256_zero(), c0);
-    b.idx[1] = 1; b.delta[1] = Fr::sub(u256_zero(), c1);
-    b.idx[2] = 2; b.delta[2] = Fr::sub(u256_zero(), c2);
-    b.idx[3] = n; b.delta[3] = c0;
-    b.idx[4] = n + 1; b.delta[4] = c1;
-    b.idx[5] = n + 2; b.delta[5] = c2;
-    hipLaunchKernelGGL(k_blind_map, dim3(1), dim3(64), 0, s, z_ss, P.bmap(b, true));
-    PBF_HIP(hipGetLastError());
-  }
+  hipLaunchKernelGGL(k_blind_map, dim3(1), dim3(64), 0, s, z_ss, P.bmap(blind_z(n, S.bl), true));
+  PBF_HIP(hipGetLastError());
   {
     const uint64_t* ss[1] = {z_ss};
     uint64_t* cr[1] = {z_cr};
@@ -1591,28 +1577,7 @@ static int prove_sharded(Prover& P, ProverBufs& B, int mode, bool pk_on, bool pk
     if ((rc = P.coset_ntt_ss(5, ss, lens, bases, CE(0)))) return rc;  // slots 0 1 2 3 and 13 (after 3)
   }
   QuotArgs qa;
-  qa.a = CE(0); qa.b = CE(1); qa.c = CE(2); qa.z = CE(3); qa.ql = CE(4); qa.qr = CE(5); qa.qo = CE(6);
-  qa.qm = CE(7); qa.qc = CE(8); qa.s1 = CE(9); qa.s2 = CE(10); qa.s3 = CE(11); qa.l1 = CE(12);
-  qa.zw = CE(13);
-  qa.N = NE;
-  qa.N_all = P.N;
-  qa.blk = P.blk();
-  qa.beta0 = Fr::from_mont(beta);
-  qa.gamma0 = Fr::from_mont(gamma);
-  qa.alpha4 = Fr::to_mont(Fr::to_mont(Fr::to_mont(alpha)));
-  qa.k1 = k1; qa.k2 = k2;
-  qa.alpha2 = Fr::mul(alpha, alpha);
-  qa.g = P.g; qa.wN = P.omegaN;
-  {
-    const U256 gn = hpow64(P.g, n), w4 = hpow64(P.omegaN, n);
-    U256 x = gn;
-    for (int j = 0; j < 4; ++j) {
-      const U256 d = Fr::sub(x, one);
-      if (Fr::is_zero(d)) return fail(PBF_EINVAL, "coset meets H");
-      qa.zh_inv[j] = hinvm(d);
-      x = Fr::mul(x, w4);
-    }
-  }
+  if ((rc = quot_args(S, CE(13), qa))) return rc;
   launch_quotient(qa, Wq, ctx->options.num("ntt256.l29", 1) != 0, s);
   PBF_HIP(hipGetLastError());
   if ((rc = P.coset_intt_ss(Wq, t_ss))) return rc;
@@ -1632,22 +1597,12 @@ static int prove_sharded(Prover& P, ProverBufs& B, int mode, bool pk_on, bool pk
   P.mark("round 3 (sharded coset NTTs, quotient, 3 MSM)");
 
   // ---- round 4: evaluations at z (plonk.rs:393-399) as per-rank partial sums over the CR
-  // ranges (full-length key polynomials: the same range of their coefficients), all-gathered
-  const uint64_t lo = P.crlo(), span = P.crlen();
-  auto eval = [&](int np, const uint64_t* const* polys, const bool* full, const uint64_t* lens, const U256* xs,
-                  U256* res) -> int {
-    EvalArgs e;
-    uint64_t maxlen = 1;
-    for (int i = 0; i < np; ++i) {
-      const uint64_t cnt = full[i] ? (lens[i] > lo ? std::min<uint64_t>(lens[i] - lo, span) : 0) : P.cr_count(lens[i]);
-      e.poly[i] = full[i] ? polys[i] + 4 * lo : polys[i];
-      e.len[i] = cnt; e.x[i] = xs[i]; e.off[i] = lo;
-      maxlen = std::max(maxlen, cnt);
-    }
-    e.chunks = (maxlen + EV_T * EV_PER - 1) / (EV_T * EV_PER);
-    int rc2 = launch_eval(e, np, B.partial, (uint64_t*)B.evals.p, s);
+  // ranges, all-gathered
+  auto eval = [&](int np, const uint64_t* const* polys, const uint64_t* lens, const U256* xs, U256* res) -> int {
+    uint64_t cnt[12];
+    for (int i = 0; i < np; ++i) cnt[i] = P.cr_count(lens[i]);
+    int rc2 = fr_eval_run(polys, cnt, xs, np, P.crlo(), B.partial, (uint64_t*)B.evals.p, s);
     if (rc2) return rc2;
-    PBF_HIP(hipGetLastError());
     std::vector<U256> parts;
     if ((rc2 = P.gather((const uint64_t*)B.evals.p, np, parts))) return rc2;
     for (int i = 0; i < np; ++i) {
@@ -1656,44 +1611,28 @@ static int prove_sharded(Prover& P, ProverBufs& B, int mode, bool pk_on, bool pk
     }
     return 0;
   };
+  // linear combinations over this rank's CR range
+  auto lincomb = [&](int k, const uint64_t* const* in, const uint64_t* lens, const U256* c, const U256& c0,
+                     uint64_t* out) -> int {
+    uint64_t cnt[10];
+    for (int i = 0; i < k; ++i) cnt[i] = P.cr_count(lens[i]);
+    // the constant term is coefficient 0: rank 0's
+    return fr_lincomb_run(k, in, cnt, c, r == 0 ? c0 : u256_zero(), out, CRS, s);
+  };
   const U256 zw = Fr::mul(zc, P.omega);
-  U256 ev[10];
+  PlonkEvals e;
   {
+    U256 ev[10];
     const uint64_t* polys[10] = {abc_cr, abc_cr + 4 * CRS, abc_cr + 8 * CRS, C(8), C(9), t_cr, t_cr + 4 * CRS,
                                  t_cr + 8 * CRS, z_cr, l1};
-    const bool full[10] = {false, false, false, false, false, false, false, false, false, false};
     const uint64_t lens[10] = {n + 2, n + 2, n + 2, n, n, m, m, m, n + 3, n};
     const U256 xs[10] = {zc, zc, zc, zc, zc, zc, zc, zc, zw, zc};
-    if ((rc = eval(10, polys, full, lens, xs, ev))) return rc;
+    if ((rc = eval(10, polys, lens, xs, ev))) return rc;
+    e.a_z = ev[0]; e.b_z = ev[1]; e.c_z = ev[2]; e.s1_z = ev[3]; e.s2_z = ev[4]; e.zw_z = ev[8]; e.l1_z = ev[9];
+    e.t_z = Fr::add(Fr::add(ev[5], Fr::mul(fr_pow(zc, m), ev[6])), Fr::mul(fr_pow(zc, 2 * m), ev[7]));
   }
-  const U256 a_z = ev[0], b_z = ev[1], c_z = ev[2], s1_z = ev[3], s2_z = ev[4], zw_z = ev[8], l1_z = ev[9];
-  const U256 t_z = Fr::add(Fr::add(ev[5], Fr::mul(hpow64(zc, m), ev[6])), Fr::mul(hpow64(zc, 2 * m), ev[7]));
-  const U256 K2 = Fr::mul(Fr::mul(Fr::mul(Fr::add(Fr::add(a_z, Fr::mul(beta, zc)), gamma),
-                                          Fr::add(Fr::add(b_z, Fr::mul(Fr::mul(beta, k1), zc)), gamma)),
-                                  Fr::add(Fr::add(c_z, Fr::mul(Fr::mul(beta, k2), zc)), gamma)),
-                          alpha);
-  const U256 K3 = Fr::mul(Fr::mul(Fr::add(Fr::add(a_z, Fr::mul(beta, s1_z)), gamma),
-                                  Fr::add(Fr::add(b_z, Fr::mul(beta, s2_z)), gamma)),
-                          alpha);
-  const U256 K4 = Fr::mul(l1_z, qa.alpha2);
   const uint64_t rlen = mode == 0 ? 2 * n + 2 : n + 3;
-  // linear combinations over this rank's CR range: full-length inputs from offset lo
-  auto lincomb = [&](int k, const uint64_t* const* in, const bool* full, const uint64_t* lens, const U256* c,
-                     const U256& c0, uint64_t* out) -> int {
-    LinComb L;
-    L.k = k;
-    for (int i = 0; i < k; ++i) {
-      L.in[i] = full[i] ? in[i] + 4 * lo : in[i];
-      L.len[i] = full[i] ? (lens[i] > lo ? std::min<uint64_t>(lens[i] - lo, span) : 0) : P.cr_count(lens[i]);
-      L.c[i] = c[i];
-    }
-    L.c0 = r == 0 ? c0 : u256_zero();  // the constant term is coefficient 0: rank 0's
-    hipLaunchKernelGGL(k_lincomb, dim3(blocks_for(CRS)), dim3(256), 0, s, L, out, CRS);
-    PBF_HIP(hipGetLastError());
-    return 0;
-  };
-  // r(x) = q_m a_z b_z + q_l a_z + q_r b_z + q_o c_z + q_c + (K2 + K4) z(x) + r_3(x)
-  if (mode == 0) {  // r_3(x) = z(x) s_sigma_3(x) (beta z_w(z)) K3 (plonk.rs:414-416): on the coset
+  if (mode == 0) {  // z(x) s_sigma_3(x), the polynomial of r_3 (plonk.rs:414-416): on the coset
     hipLaunchKernelGGL(k_mul, dim3(blocks_for(NE)), dim3(256), 0, s, (const uint64_t*)CE(3), (const uint64_t*)CE(11), W2,
                        NE);
     PBF_HIP(hipGetLastError());
@@ -1703,66 +1642,48 @@ static int prove_sharded(Prover& P, ProverBufs& B, int mode, bool pk_on, bool pk
     const uint64_t off[1] = {0}, len[1] = {2 * n + 2};
     if ((rc = P.xpose(1, ss, NE, off, len, cr))) return rc;
   }
-  {
+  {  // r(x), all seven terms in one combination
     const uint64_t* in[7] = {C(6), C(3), C(4), C(5), C(7), z_cr, mode == 1 ? C(10) : r3_cr};
-    const bool full[7] = {false, false, false, false, false, false, false};
     const uint64_t lens[7] = {n, n, n, n, n, n + 3, mode == 1 ? n : 2 * n + 2};
-    const U256 c[7] = {Fr::mul(a_z, b_z), a_z, b_z, c_z, one, Fr::add(K2, K4),
-                       mode == 1 ? Fr::sub(u256_zero(), Fr::mul(Fr::mul(beta, zw_z), K3))
-                                 : Fr::mul(Fr::mul(beta, zw_z), K3)};
-    if ((rc = lincomb(7, in, full, lens, c, u256_zero(), rx))) return rc;
+    U256 c[7];
+    plonk_r_coeffs(S.ch, e, mode, c);
+    if ((rc = lincomb(7, in, lens, c, u256_zero(), rx))) return rc;
   }
-  U256 r_z;
   {
     const uint64_t* polys[1] = {rx};
-    const bool full[1] = {false};
-    const uint64_t lens[1] = {rlen};
-    const U256 xs[1] = {zc};
-    if ((rc = eval(1, polys, full, lens, xs, &r_z))) return rc;
+    if ((rc = eval(1, polys, &rlen, &zc, &e.r_z))) return rc;
   }
   P.mark("round 4 (evaluation partials, r(x))");
 
   // ---- round 5: the opening quotients (plonk.rs:430-442) on the CR ranges
-  U256 vp[7];
-  vp[0] = one;
-  for (int i = 1; i < 7; ++i) vp[i] = Fr::mul(vp[i - 1], v);
   {
     const uint64_t* in[9] = {t_cr, t_cr + 4 * CRS, t_cr + 8 * CRS, rx, abc_cr, abc_cr + 4 * CRS, abc_cr + 8 * CRS,
                              C(8), C(9)};
-    const bool full[9] = {false, false, false, false, false, false, false, false, false};
     const uint64_t lens[9] = {m, m, m, rlen, n + 2, n + 2, n + 2, n, n};
-    const U256 c[9] = {one, hpow64(zc, n + 2), hpow64(zc, 2 * n + 4), vp[1], vp[2], vp[3], vp[4], vp[5], vp[6]};
-    U256 cst = Fr::add(t_z, Fr::mul(vp[1], r_z));
-    cst = Fr::add(cst, Fr::mul(vp[2], a_z));
-    cst = Fr::add(cst, Fr::mul(vp[3], b_z));
-    cst = Fr::add(cst, Fr::mul(vp[4], c_z));
-    cst = Fr::add(cst, Fr::mul(vp[5], s1_z));
-    cst = Fr::add(cst, Fr::mul(vp[6], s2_z));
-    if ((rc = lincomb(9, in, full, lens, c, Fr::sub(u256_zero(), cst), numer))) return rc;
+    U256 c[9];
+    const U256 c0 = plonk_wz_coeffs(S.ch, e, n, c);
+    if ((rc = lincomb(9, in, lens, c, c0, numer))) return rc;
   }
   const uint64_t lnum = rlen > m ? rlen : m;
   const uint64_t wlen = lnum - 1;
   if ((rc = P.synth_div_cr(numer, lnum, zc, u256_zero(), wz, "W_z division left a remainder (plonk.rs:438)"))) return rc;
   if ((rc = P.commit_cr(wz, wlen, 7))) return rc;
-  if ((rc = P.synth_div_cr(z_cr, n + 3, zw, zw_z, wzw, "W_zw division left a remainder (plonk.rs:442)"))) return rc;
+  if ((rc = P.synth_div_cr(z_cr, n + 3, zw, e.zw_z, wzw, "W_zw division left a remainder (plonk.rs:442)"))) return rc;
   if ((rc = P.commit_cr(wzw, n + 2, 8))) return rc;
-  uint64_t pts[9][8];
-  if ((rc = P.finish_commits(9, pts))) return rc;
+  if ((rc = P.finish_commits(9, (uint64_t(*)[8])S.out_pts))) return rc;
   P.mark("round 5 (sharded divisions, 2 MSM)");
-  for (int i = 0; i < 9; ++i) memcpy(out_pts + 8 * i, pts[i], 64);
-  const U256 fo[7] = {a_z, b_z, c_z, s1_z, s2_z, r_z, zw_z};
-  for (int i = 0; i < 7; ++i) hout(out_f + 4 * i, fo[i]);
+  write_proof_fields(S.out_f, e);
   return 0;
 }
 
-// Plonk::prove; comm == null (or world 1): one GPU; else this rank's part of the multi-GPU
-// split (pbf.h pbf_plonk_prove_bn254_sharded_dev)
-static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
-                      const uint64_t* d_abc, const uint64_t* chal, const uint64_t* rnd, const uint64_t* k1k2,
-                      const uint64_t* d_srs, size_t srs_m, int mode, uint64_t* out_pts, uint64_t* out_f,
-                      void* stream) {
-  if (!ctx || !d_q || !d_copies || !d_abc || !chal || !rnd || !k1k2 || !d_srs || !out_pts || !out_f)
-    return fail(PBF_EINVAL, "null argument");
+// What both provers need before their rounds: the arguments validated, the Prover initialised
+// (comm == null or world 1: one GPU; else this rank's layouts), the proving-key state, the
+// scratch buffers sized and the slot tables. S.mode, the device inputs and the outputs are set by
+// the caller.
+static int prove_setup(ProveState& S, pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64_t* chal,
+                       const uint64_t* rnd, const uint64_t* k1k2, const uint64_t* d_srs, size_t srs_m, void* stream) {
+  const int mode = S.mode;
+  const uint64_t *d_q = S.d_q, *d_copies = S.d_copies;
   if (n < 8 || (n & (n - 1))) return fail(PBF_EINVAL, "n must be a power of two >= 8");
   if (mode != 0 && mode != 1) return fail(PBF_EINVAL, "mode must be 0 (reference r_3) or 1 (paper)");
   PBF_HIP(hipSetDevice(ctx->device));
@@ -1776,18 +1697,17 @@ static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64
   for (int i = 0; i < 9; ++i)
     if (Fr::geq_p(u256_from_u64(rnd + 4 * i))) return fail(PBF_EINVAL, "blinder not canonical");
 
-  Prover P;
+  Prover& P = S.P;
   P.ctx = ctx;
   P.s = (hipStream_t)stream;
   P.timing = ctx->options.num("prover.timing", 0) != 0;
   P.mark("start");
   P.n = n;
   P.N = 4 * n;
-  P.log_n = log_n;
-  P.omega = hroot(log_n);
-  P.omegaN = hroot(log_n + 2);
+  P.omega = fr_root_of_unity(log_n);
+  P.omegaN = fr_root_of_unity(log_n + 2);
   P.g = hm64(5);  // coset shift: a quadratic non-residue, outside every 2^k subgroup
-  P.g_inv = hinvm(P.g);
+  P.g_inv = fr_inv(P.g);
   hout(P.w_plain, P.omega);
   hout(P.wN_plain, P.omegaN);
   if (comm && comm->world > 1) {
@@ -1813,17 +1733,16 @@ static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64
   }
   const hipStream_t s = P.s;
   const uint64_t N = P.N;
-  const U256 one = fr_one_m();
   const U256 k1 = hm(k1k2), k2 = hm(k1k2 + 4);
   // Plonk::new asserts (plonk.rs:133-138): k1, k2 not in H, k2 not in k1 H
-  if (heq1(hpow64(k1, n)) || heq1(hpow64(k2, n)) || heq1(hpow64(Fr::mul(k2, hinvm(k1)), n)) || Fr::is_zero(k1) ||
+  if (heq1(fr_pow(k1, n)) || heq1(fr_pow(k2, n)) || heq1(fr_pow(Fr::mul(k2, fr_inv(k1)), n)) || Fr::is_zero(k1) ||
       Fr::is_zero(k2))
     return fail(PBF_EINVAL, "k1/k2 do not give disjoint cosets of H");
-  const U256 alpha = hm(chal), beta = hm(chal + 4), gamma = hm(chal + 8), zc = hm(chal + 12), v = hm(chal + 16);
-  U256 bl[9];
-  for (int i = 0; i < 9; ++i) bl[i] = hm(rnd + 4 * i);
+  S.ch.alpha = hm(chal); S.ch.beta = hm(chal + 4); S.ch.gamma = hm(chal + 8); S.ch.z = hm(chal + 12);
+  S.ch.v = hm(chal + 16); S.ch.k1 = k1; S.ch.k2 = k2;
+  for (int i = 0; i < 9; ++i) S.bl[i] = hm(rnd + 4 * i);
 
-  ProverBufs B(ctx);  // context-owned scratch (one ctx per host thread, pbf.h)
+  ProverBufs& B = S.B;
   const uint64_t E = 32;           // bytes per element
   const uint64_t CS = n + 8;       // coefficient slot (room for blinding terms up to x^(n+2))
   int rc;
@@ -1835,10 +1754,9 @@ static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64
   // Option prover.pk = 0 recomputes them per proof, as the reference does (plonk.rs:233-243,
   // 339-370).
   const bool pk_on = ctx->options.num("prover.pk", 1) != 0;  // sharded too: this rank's coset blocks
-  bool pk_hit = false;
-  uint64_t* pkcoef = nullptr;
+  S.pk_on = pk_on;
   uint64_t* pkcoset = nullptr;
-  std::vector<uint64_t> pk_key;
+  std::vector<uint64_t>& pk_key = S.pk_key;
   if (pk_on) {
     const SnapItem items[2] = {{"q", d_q, 20 * (uint64_t)n}, {"copies", d_copies, 6 * (uint64_t)n}};
     bool same = false;
@@ -1850,10 +1768,10 @@ static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64
     DevBuf& kc = ctx->buf("pk.coef");
     DevBuf& ks = ctx->buf("pk.coset");
     if ((rc = kc.ensure(8 * (P.G > 1 ? P.CRS() : CS) * E)) || (rc = ks.ensure(9 * P.count() * E))) return rc;
-    pkcoef = (uint64_t*)kc.p;
+    S.pkcoef = (uint64_t*)kc.p;
     pkcoset = (uint64_t*)ks.p;
-    pk_hit = ctx->pk_key == pk_key;
-    if (!pk_hit) ctx->pk_key.clear();  // the slots are rewritten below; valid again once complete
+    S.pk_hit = ctx->pk_key == pk_key;
+    if (!S.pk_hit) ctx->pk_key.clear();  // the slots are rewritten below; valid again once complete
   }
   // sharded: full-length scratch only where the proving key is built (the circuit's polynomials
   // on every rank); the witness-dependent vectors live in this rank's SS / CR pieces ("pv.sh")
@@ -1883,27 +1801,38 @@ static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64
       if ((rc = msm_fixed_table(ctx, d_srs + 8 * P.crlo(), P.srs_n, s, &P.srs_tbl))) return rc;
     }
   }
-  uint64_t* hpow = (uint64_t*)B.hpow.p;
-  uint64_t* sigma = (uint64_t*)B.sigma.p;
+  // the slot tables (ProveState)
   uint64_t* coef = (uint64_t*)B.coef.p;
-  // slots: 0 a, 1 b, 2 c, 3 q_l, 4 q_r, 5 q_o, 6 q_m, 7 q_c, 8 s1, 9 s2, 10 s3 (3.. in the proving key)
-  uint64_t* cslot[11];
   const uint64_t cstride = sharded ? P.CRS() : CS;  // sharded: the circuit polynomials' CR ranges
-  for (int k = 0; k < 11; ++k) cslot[k] = (pk_on && k >= 3) ? pkcoef + 4 * cstride * (k - 3) : coef + 4 * cstride * k;
-  auto C = [&](int k) { return cslot[k]; };
+  for (int k = 0; k < 11; ++k)
+    S.cslot[k] = (pk_on && k >= 3) ? S.pkcoef + 4 * cstride * (k - 3) : coef + 4 * cstride * k;
   uint64_t* coset = (uint64_t*)B.coset.p;
   const uint64_t NE = P.count();  // coset evaluations held here (N; nl = N / G when sharded)
-  uint64_t* ceslot[14];
   for (int k = 0; k < 14; ++k)
-    ceslot[k] = (pk_on && k >= 4 && k <= 12)  ? pkcoset + 4 * NE * (k - 4)
-                : ((pk_on || sharded) && k == 13) ? coset + 4 * NE * 4        // z(w x) after a b c z
-                : (sharded && k >= 4 && k <= 12)  ? coset + 4 * NE * (k + 1)  // no key: circuit slots after
-                                                  : coset + 4 * NE * k;
-  auto CE = [&](int k) { return ceslot[k]; };
-  // coset slots: 0 a 1 b 2 c 3 z 4 ql 5 qr 6 qo 7 qm 8 qc 9 s1 10 s2 11 s3 12 l1 [13 z(w x), sharded]
-  if (sharded)
-    return prove_sharded(P, B, mode, pk_on, pk_hit, pk_key, cslot, ceslot, d_q, d_copies, d_abc, k1, k2, bl, alpha, beta,
-                         gamma, zc, v, out_pts, out_f);
+    S.ceslot[k] = (pk_on && k >= 4 && k <= 12)  ? pkcoset + 4 * NE * (k - 4)
+                  : ((pk_on || sharded) && k == 13) ? coset + 4 * NE * 4        // z(w x) after a b c z
+                  : (sharded && k >= 4 && k <= 12)  ? coset + 4 * NE * (k + 1)  // no key: circuit slots after
+                                                    : coset + 4 * NE * k;
+  return 0;
+}
+
+// ---- Plonk::prove on one GPU: the reference's rounds on whole polynomials
+static int prove_single(ProveState& S) {
+  Prover& P = S.P;
+  ProverBufs& B = S.B;
+  pbf_ctx* ctx = P.ctx;
+  const hipStream_t s = P.s;
+  const int mode = S.mode;
+  const bool pk_on = S.pk_on, pk_hit = S.pk_hit;
+  const uint64_t *d_q = S.d_q, *d_copies = S.d_copies, *d_abc = S.d_abc;
+  const U256 &k1 = S.ch.k1, &k2 = S.ch.k2, &beta = S.ch.beta, &gamma = S.ch.gamma, &zc = S.ch.z;
+  const uint64_t n = P.n, N = P.N, NE = N, E = 32, CS = n + 8;
+  const U256 one = fr_one_m();
+  uint64_t *hpow = (uint64_t*)B.hpow.p, *sigma = (uint64_t*)B.sigma.p, *coef = (uint64_t*)B.coef.p;
+  uint64_t* pkcoef = S.pkcoef;
+  auto C = [&](int k) { return S.cslot[k]; };
+  auto CE = [&](int k) { return S.ceslot[k]; };
+  int rc;
   uint64_t* work = (uint64_t*)B.work.p;
   uint64_t* W0 = work;
   uint64_t* W1 = work + 4 * N;
@@ -1917,11 +1846,7 @@ static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64
   P.mark("satisfies");
 
   // ---- h = w^i, sigma labels (plonk.rs:124, 181-189, 222-224)
-  hipLaunchKernelGGL(k_powers29, dim3(blocks_for((n + PV_CHUNK - 1) / PV_CHUNK)), dim3(256), 0, s, hpow, (uint64_t)n,
-                     powers_tab29(P.omega, one));
-  hipLaunchKernelGGL(k_sigma, dim3(blocks_for(3 * n)), dim3(256), 0, s, d_copies, (const uint64_t*)hpow, (uint64_t)n,
-                     (uint64_t)0, (uint64_t)n, k1, k2, sigma, P.d_bad);
-  PBF_HIP(hipGetLastError());
+  if ((rc = sigma_table_run(n, P.omega, k1, k2, d_copies, hpow, sigma, P.d_bad, s))) return rc;
   // ---- interpolate_at_h of a b c q_l q_r q_o q_m q_c s1 s2 s3 = INTT (plonk.rs:233-243)
   // every slot's first n coefficients are written below (INTT outputs): only the tails [n, CS)
   // are cleared (round 6: the whole slots were, 1.5 GB at 2^24 rows)
@@ -1941,22 +1866,11 @@ static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64
   }
   P.mark(pk_hit ? "interpolate (3 INTT, key)" : "interpolate (11 INTT)");
   // ---- round 1: a(x) = (b2 + b1 x)(x^n - 1) + f_a(x), likewise b, c (plonk.rs:250-252)
-  for (int k = 0; k < 3; ++k) {
-    const U256 lo = bl[2 * k + 1], hi = bl[2 * k];  // (b2, b1), (b4, b3), (b6, b5)
-    Blind b;
-    b.count = 4;
-    b.idx[0] = 0; b.delta[0] = Fr::sub(u256_zero(), lo);
-    b.idx[1] = 1; b.delta[1] = Fr::sub(u256_zero(), hi);
-    b.idx[2] = n; b.delta[2] = lo;
-    b.idx[3] = n + 1; b.delta[3] = hi;
-    hipLaunchKernelGGL(k_blind, dim3(1), dim3(64), 0, s, C(k), b);
-  }
+  for (int k = 0; k < 3; ++k)  // (b2, b1), (b4, b3), (b6, b5)
+    hipLaunchKernelGGL(k_blind, dim3(1), dim3(64), 0, s, C(k), blind_abc(n, S.bl[2 * k + 1], S.bl[2 * k]));
   PBF_HIP(hipGetLastError());
-  uint64_t pts[9][8];
-  {
-    for (int k = 0; k < 3; ++k)
-      if ((rc = P.commit(C(k), n + 2, k))) return rc;
-  }
+  for (int k = 0; k < 3; ++k)
+    if ((rc = P.commit(C(k), n + 2, k))) return rc;
   P.mark("round 1 commits (3 MSM)");
 
   // ---- round 2: accumulator (plonk.rs:278-313)
@@ -1980,19 +1894,8 @@ static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64
     PBF_HIP(hipGetLastError());
   }
   if ((rc = P.ntt(P.w_plain, acc, acc, n, 1, 1))) return rc;  // acc_x
-  {
-    Blind b;  // z(x) = (b9 + b8 x + b7 x^2)(x^n - 1) + acc(x)   (plonk.rs:309)
-    b.count = 6;
-    const U256 c0 = bl[8], c1 = bl[7], c2 = bl[6];
-    b.idx[0] = 0; b.delta[0] = Fr::sub(u256_zero(), c0);
-    b.idx[1] = 1; b.delta[1] = Fr::sub(u256_zero(), c1);
-    b.idx[2] = 2; b.delta[2] = Fr::sub(u256_zero(), c2);
-    b.idx[3] = n; b.delta[3] = c0;
-    b.idx[4] = n + 1; b.delta[4] = c1;
-    b.idx[5] = n + 2; b.delta[5] = c2;
-    hipLaunchKernelGGL(k_blind, dim3(1), dim3(64), 0, s, acc, b);
-    PBF_HIP(hipGetLastError());
-  }
+  hipLaunchKernelGGL(k_blind, dim3(1), dim3(64), 0, s, acc, blind_z(n, S.bl));
+  PBF_HIP(hipGetLastError());
   uint64_t* zx = acc;  // length n+3
   P.mark("round 2 accumulator");
   if ((rc = P.commit(zx, n + 3, 3))) return rc;
@@ -2001,7 +1904,7 @@ static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64
   // ---- round 3: quotient on the coset g H_4n (plonk.rs:326-382)
   const int cmap[13] = {0, 1, 2, -1, 3, 4, 5, 6, 7, 8, 9, 10, -2};  // coef slot per coset slot
   // l_1(x) = interpolate([1, 0, ..., 0]) = n^-1 (1 + x + ... + x^(n-1)) (plonk.rs:328-332)
-  const U256 ninv = hinvm(hm64(n));
+  const U256 ninv = fr_inv(hm64(n));
   {
     uint64_t* l1 = (uint64_t*)B.tmp0.p;
     hipLaunchKernelGGL(k_powers29, dim3(blocks_for((n + PV_CHUNK - 1) / PV_CHUNK)), dim3(256), 0, s, l1, (uint64_t)n,
@@ -2009,27 +1912,20 @@ static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64
     PBF_HIP(hipGetLastError());
   }
   {
-    const uint64_t* srcs[14];
-    uint64_t lens[14];
-    U256 bases[14];
+    const uint64_t* srcs[13];
+    uint64_t lens[13];
+    U256 bases[13];
     for (int k = 0; k < 13; ++k) {
       if (cmap[k] == -1) { srcs[k] = zx; lens[k] = n + 3; }
       else if (cmap[k] == -2) { srcs[k] = (const uint64_t*)B.tmp0.p; lens[k] = n; }
       else { srcs[k] = C(cmap[k]); lens[k] = cmap[k] < 3 ? n + 2 : n; }
       bases[k] = P.g;
     }
-    // sharded: z(w x) gets its own slot (coefficients z_j w^j) instead of reading z at index i+4,
-    // which may sit in another rank's block
-    srcs[13] = zx; lens[13] = n + 3; bases[13] = Fr::mul(P.g, P.omega);
-    if (pk_on) {  // a b c z (and z(w x) when sharded) per proof, all canonical; the 9 circuit
-                  // slots once per proving key
-      const uint64_t* ps[5] = {srcs[0], srcs[1], srcs[2], srcs[3], srcs[13]};
-      const uint64_t pl[5] = {lens[0], lens[1], lens[2], lens[3], lens[13]};
-      const U256 pb[5] = {bases[0], bases[1], bases[2], bases[3], bases[13]};
-      if ((rc = P.coset_ntt_batch(4, ps, pl, pb, CE(0)))) return rc;
+    if (pk_on) {  // a b c z per proof, all canonical; the 9 circuit slots once per proving key
+      if ((rc = P.coset_ntt_batch(4, srcs, lens, bases, CE(0)))) return rc;
       if (!pk_hit) {
         if ((rc = P.coset_ntt_batch(9, srcs + 4, lens + 4, bases + 4, CE(4), QUOT_DEG + 4))) return rc;
-        ctx->pk_key = pk_key;
+        ctx->pk_key = S.pk_key;
       }
     } else if ((rc = P.coset_ntt_batch(13, srcs, lens, bases, CE(0), QUOT_DEG))) {
       return rc;
@@ -2037,30 +1933,7 @@ static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64
   }
   P.mark(pk_hit ? "round 3 coset NTTs (4, key)" : "round 3 coset NTTs (13)");
   QuotArgs qa;
-  qa.a = CE(0); qa.b = CE(1); qa.c = CE(2); qa.z = CE(3); qa.ql = CE(4); qa.qr = CE(5); qa.qo = CE(6);
-  qa.qm = CE(7); qa.qc = CE(8); qa.s1 = CE(9); qa.s2 = CE(10); qa.s3 = CE(11); qa.l1 = CE(12);
-  qa.zw = nullptr;
-  qa.N = NE;
-  qa.N_all = N;
-  qa.blk = P.blk();
-  // constants at the R-degrees the quotient's terms need (QuotArgs): Montgomery form is degree 1
-  qa.beta0 = Fr::from_mont(beta);
-  qa.gamma0 = Fr::from_mont(gamma);
-  qa.alpha4 = Fr::to_mont(Fr::to_mont(Fr::to_mont(alpha)));
-  qa.k1 = k1; qa.k2 = k2;
-  qa.alpha2 = Fr::mul(alpha, alpha);
-  qa.g = P.g; qa.wN = P.omegaN;
-  {
-    // Z_H(g w_N^i) = g^n w_4^(i mod 4) - 1
-    const U256 gn = hpow64(P.g, n), w4 = hpow64(P.omegaN, n);
-    U256 x = gn;
-    for (int j = 0; j < 4; ++j) {
-      const U256 d = Fr::sub(x, one);
-      if (Fr::is_zero(d)) return fail(PBF_EINVAL, "coset meets H");
-      qa.zh_inv[j] = hinvm(d);
-      x = Fr::mul(x, w4);
-    }
-  }
+  if ((rc = quot_args(S, nullptr, qa))) return rc;  // z(w x): z at index i + 4
   uint64_t* tq = (uint64_t*)B.t.p;
   launch_quotient(qa, W0, ctx->options.num("ntt256.l29", 1) != 0, s);
   PBF_HIP(hipGetLastError());
@@ -2082,134 +1955,91 @@ static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64
   // ---- round 4: evaluations at z (plonk.rs:393-399), linearisation r(x) (:401-422)
   const U256 zw = Fr::mul(zc, P.omega);
   auto eval = [&](int np, const uint64_t* const* polys, const uint64_t* lens, const U256* xs, U256* res) -> int {
-    EvalArgs e;
-    uint64_t maxlen = 0;
-    for (int i = 0; i < np; ++i) {
-      e.poly[i] = polys[i]; e.len[i] = lens[i]; e.x[i] = xs[i]; e.off[i] = 0;
-      if (lens[i] > maxlen) maxlen = lens[i];
-    }
-    e.chunks = (maxlen + EV_T * EV_PER - 1) / (EV_T * EV_PER);
-    int rc2 = launch_eval(e, np, B.partial, (uint64_t*)B.evals.p, s);
+    int rc2 = fr_eval_run(polys, lens, xs, np, 0, B.partial, (uint64_t*)B.evals.p, s);
     if (rc2) return rc2;
-    PBF_HIP(hipGetLastError());
     std::vector<uint64_t> h(4 * np);
     PBF_HIP(hipMemcpyAsync(h.data(), B.evals.p, 4 * np * 8, hipMemcpyDeviceToHost, s));
     PBF_HIP(hipStreamSynchronize(s));
     for (int i = 0; i < np; ++i) res[i] = hm(h.data() + 4 * i);
     return 0;
   };
-  U256 ev[8];
+  PlonkEvals e;
   {
+    U256 ev[8];  // t(z) from t as one polynomial of 3m coefficients
     const uint64_t* polys[8] = {C(0), C(1), C(2), C(8), C(9), tq, zx, (const uint64_t*)B.tmp0.p};
     const uint64_t lens[8] = {n + 2, n + 2, n + 2, n, n, 3 * m, n + 3, n};
     const U256 xs[8] = {zc, zc, zc, zc, zc, zc, zw, zc};
     if ((rc = eval(8, polys, lens, xs, ev))) return rc;
+    e.a_z = ev[0]; e.b_z = ev[1]; e.c_z = ev[2]; e.s1_z = ev[3]; e.s2_z = ev[4]; e.t_z = ev[5]; e.zw_z = ev[6];
+    e.l1_z = ev[7];
   }
-  const U256 a_z = ev[0], b_z = ev[1], c_z = ev[2], s1_z = ev[3], s2_z = ev[4], t_z = ev[5], zw_z = ev[6];
-  const U256 l1_z = ev[7];
-  (void)t_z;
-  // r(x) = q_m a_z b_z + q_l a_z + q_r b_z + q_o c_z + q_c + K2 z(x) + r_3(x) + L1(z) alpha^2 z(x)
-  const U256 K2 = Fr::mul(Fr::mul(Fr::mul(Fr::add(Fr::add(a_z, Fr::mul(beta, zc)), gamma),
-                                          Fr::add(Fr::add(b_z, Fr::mul(Fr::mul(beta, k1), zc)), gamma)),
-                                  Fr::add(Fr::add(c_z, Fr::mul(Fr::mul(beta, k2), zc)), gamma)),
-                          alpha);
-  const U256 K3 = Fr::mul(Fr::mul(Fr::add(Fr::add(a_z, Fr::mul(beta, s1_z)), gamma),
-                                  Fr::add(Fr::add(b_z, Fr::mul(beta, s2_z)), gamma)),
-                          alpha);
-  const U256 K4 = Fr::mul(l1_z, qa.alpha2);
   const uint64_t rlen = mode == 0 ? 2 * n + 2 : n + 3;
   uint64_t* rx = W1;  // r(x) coefficients (length rlen, N slot)
   {
-    LinComb L;
-    L.k = 7;
-    L.in[0] = C(6); L.len[0] = n; L.c[0] = Fr::mul(a_z, b_z);
-    L.in[1] = C(3); L.len[1] = n; L.c[1] = a_z;
-    L.in[2] = C(4); L.len[2] = n; L.c[2] = b_z;
-    L.in[3] = C(5); L.len[3] = n; L.c[3] = c_z;
-    L.in[4] = C(7); L.len[4] = n; L.c[4] = one;
-    L.in[5] = zx; L.len[5] = n + 3; L.c[5] = Fr::add(K2, K4);
-    if (mode == 1) {  // paper: - beta z_w(z) K3 s_sigma_3(x)
-      L.in[6] = C(10); L.len[6] = n; L.c[6] = Fr::sub(u256_zero(), Fr::mul(Fr::mul(beta, zw_z), K3));
-    } else {
-      L.k = 6;
-    }
-    L.c0 = u256_zero();
-    // only the rlen coefficients r(x) has are written (round 6; the N-long tail of zeros was
-    // never read: the evaluation, the r_3 sum and the W_z numerator stop at rlen)
-    hipLaunchKernelGGL(k_lincomb, dim3(blocks_for(rlen)), dim3(256), 0, s, L, rx, rlen);
-    PBF_HIP(hipGetLastError());
+    U256 c[7];
+    plonk_r_coeffs(S.ch, e, mode, c);
+    const uint64_t* in[7] = {C(6), C(3), C(4), C(5), C(7), zx, C(10)};
+    const uint64_t lens[7] = {n, n, n, n, n, n + 3, n};
+    // mode 1: all seven terms; mode 0: the first six, r_3 below. Only the rlen coefficients r(x)
+    // has are written (round 6; the N-long tail of zeros was never read: the evaluation, the r_3
+    // sum and the W_z numerator stop at rlen)
+    if ((rc = fr_lincomb_run(mode == 1 ? 7 : 6, in, lens, c, u256_zero(), rx, rlen, s))) return rc;
     if (mode == 0) {
       // r_3(x) = z(x) s_sigma_3(x) (beta z_w(z)) K3 (plonk.rs:414-416): the product on the coset
       hipLaunchKernelGGL(k_mul, dim3(blocks_for(NE)), dim3(256), 0, s, (const uint64_t*)CE(3), (const uint64_t*)CE(11),
                          W2, NE);
       PBF_HIP(hipGetLastError());
       if ((rc = P.coset_intt(W2, W0))) return rc;
-      LinComb L2;
-      L2.k = 2;
-      L2.in[0] = rx; L2.len[0] = rlen; L2.c[0] = one;  // z s_sigma_3 has rlen = 2n + 2 coefficients
-      L2.in[1] = W0; L2.len[1] = rlen; L2.c[1] = Fr::mul(Fr::mul(beta, zw_z), K3);
-      L2.c0 = u256_zero();
-      hipLaunchKernelGGL(k_lincomb, dim3(blocks_for(rlen)), dim3(256), 0, s, L2, W2, rlen);
-      PBF_HIP(hipGetLastError());
+      const uint64_t* in2[2] = {rx, W0};
+      const uint64_t lens2[2] = {rlen, rlen};  // z s_sigma_3 has rlen = 2n + 2 coefficients
+      const U256 c2[2] = {one, c[6]};
+      if ((rc = fr_lincomb_run(2, in2, lens2, c2, u256_zero(), W2, rlen, s))) return rc;
       PBF_HIP(hipMemcpyAsync(rx, W2, rlen * E, hipMemcpyDeviceToDevice, s));
     }
   }
-  U256 r_z;
   {
     const uint64_t* polys[1] = {rx};
-    const uint64_t lens[1] = {rlen};
-    const U256 xs[1] = {zc};
-    if ((rc = eval(1, polys, lens, xs, &r_z))) return rc;
+    if ((rc = eval(1, polys, &rlen, &zc, &e.r_z))) return rc;
   }
   P.mark("round 4 evals + r(x)");
 
-  // ---- round 5: W_z = [t_lo + z^(n+2) t_mid + z^(2n+4) t_hi - t_z + v (r - r_z) + v^2 (a - a_z)
-  //      + v^3 (b - b_z) + v^4 (c - c_z) + v^5 (s1 - s1_z) + v^6 (s2 - s2_z)] / (x - z)   (:430-439)
+  // ---- round 5: W_z = numerator / (x - z), W_zw = (z(x) - z_w(z)) / (x - z w) (plonk.rs:430-442)
+  // by synthetic division on the coefficients
   const uint64_t lnum = rlen > m ? rlen : m;  // numerator coefficients (t parts m, r rlen, a/b/c n+2)
-  U256 vp[7];
-  vp[0] = one;
-  for (int i = 1; i < 7; ++i) vp[i] = Fr::mul(vp[i - 1], v);
   {
-    LinComb L;  // numerator coefficients into W2 (constant term folded: vanishes at z)
-    L.k = 10;
-    const U256 zn2 = hpow64(zc, n + 2), z2n4 = hpow64(zc, 2 * n + 4);
-    L.in[0] = tq; L.len[0] = m; L.c[0] = one;
-    L.in[1] = tq + 4 * m; L.len[1] = m; L.c[1] = zn2;
-    L.in[2] = tq + 8 * m; L.len[2] = m; L.c[2] = z2n4;
-    L.in[3] = rx; L.len[3] = rlen; L.c[3] = vp[1];
-    L.in[4] = C(0); L.len[4] = n + 2; L.c[4] = vp[2];
-    L.in[5] = C(1); L.len[5] = n + 2; L.c[5] = vp[3];
-    L.in[6] = C(2); L.len[6] = n + 2; L.c[6] = vp[4];
-    L.in[7] = C(8); L.len[7] = n; L.c[7] = vp[5];
-    L.in[8] = C(9); L.len[8] = n; L.c[8] = vp[6];
-    L.k = 9;
-    U256 cst = Fr::add(t_z, Fr::mul(vp[1], r_z));
-    cst = Fr::add(cst, Fr::mul(vp[2], a_z));
-    cst = Fr::add(cst, Fr::mul(vp[3], b_z));
-    cst = Fr::add(cst, Fr::mul(vp[4], c_z));
-    cst = Fr::add(cst, Fr::mul(vp[5], s1_z));
-    cst = Fr::add(cst, Fr::mul(vp[6], s2_z));
-    L.c0 = Fr::sub(u256_zero(), cst);
-    hipLaunchKernelGGL(k_lincomb, dim3(blocks_for(lnum)), dim3(256), 0, s, L, W2, lnum);  // what the division reads
-    PBF_HIP(hipGetLastError());
+    U256 c[9];
+    const U256 c0 = plonk_wz_coeffs(S.ch, e, n, c);  // the constant term folded: vanishes at z
+    const uint64_t* in[9] = {tq, tq + 4 * m, tq + 8 * m, rx, C(0), C(1), C(2), C(8), C(9)};
+    const uint64_t lens[9] = {m, m, m, rlen, n + 2, n + 2, n + 2, n, n};
+    if ((rc = fr_lincomb_run(9, in, lens, c, c0, W2, lnum, s))) return rc;  // what the division reads
   }
-  // W_z = numerator / (x - z), W_zw = (z(x) - z_w(z)) / (x - z w) (plonk.rs:430-442) by
-  // synthetic division on the coefficients (replicated on every rank of a sharded prove)
   const uint64_t wlen = lnum - 1;  // = max(rlen - 1, m)
   if ((rc = P.synth_div(W2, lnum, zc, u256_zero(), W1, "W_z division left a remainder (plonk.rs:438)"))) return rc;
   uint64_t* W3 = W0;  // W1 still feeds the W_z commitment's MSM
-  if ((rc = P.synth_div(zx, n + 3, zw, zw_z, W3, "W_zw division left a remainder (plonk.rs:442)"))) return rc;
-  {
-    if ((rc = P.commit(W1, wlen, 7))) return rc;
-    if ((rc = P.commit(W3, n + 2, 8))) return rc;
-  }
-  if ((rc = P.finish_commits(9, pts))) return rc;
+  if ((rc = P.synth_div(zx, n + 3, zw, e.zw_z, W3, "W_zw division left a remainder (plonk.rs:442)"))) return rc;
+  if ((rc = P.commit(W1, wlen, 7))) return rc;
+  if ((rc = P.commit(W3, n + 2, 8))) return rc;
+  if ((rc = P.finish_commits(9, (uint64_t(*)[8])S.out_pts))) return rc;
   P.mark("round 5 openings + 2 MSM");
-
-  for (int i = 0; i < 9; ++i) memcpy(out_pts + 8 * i, pts[i], 64);
-  const U256 fo[7] = {a_z, b_z, c_z, s1_z, s2_z, r_z, zw_z};
-  for (int i = 0; i < 7; ++i) hout(out_f + 4 * i, fo[i]);
+  write_proof_fields(S.out_f, e);
   return 0;
+}
+
+// Plonk::prove; comm == null (or world 1): one GPU; else this rank's part of the multi-GPU
+// split (pbf.h pbf_plonk_prove_bn254_sharded_dev)
+static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
+                      const uint64_t* d_abc, const uint64_t* chal, const uint64_t* rnd, const uint64_t* k1k2,
+                      const uint64_t* d_srs, size_t srs_m, int mode, uint64_t* out_pts, uint64_t* out_f,
+                      void* stream) {
+  if (!ctx || !d_q || !d_copies || !d_abc || !chal || !rnd || !k1k2 || !d_srs || !out_pts || !out_f)
+    return fail(PBF_EINVAL, "null argument");
+  ProveState S(ctx);
+  S.mode = mode;
+  S.d_q = d_q; S.d_copies = d_copies; S.d_abc = d_abc;
+  S.out_pts = out_pts; S.out_f = out_f;
+  int rc = prove_setup(S, ctx, comm, n, chal, rnd, k1k2, d_srs, srs_m, stream);
+  if (rc) return rc;
+  return S.P.G > 1 ? prove_sharded(S) : prove_single(S);
 }
 
 extern "C" int pbf_plonk_prove_bn254_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
@@ -2249,265 +2079,6 @@ extern "C" int pbf_plonk_prove_bn254(pbf_ctx* ctx, size_t n, const uint64_t* q, 
   if (rc) return rc;
   PBF_HIP(hipStreamSynchronize(s));
   return 0;
-}
-
-// ---------------------------------------------------------------- Plonk::verify
-namespace {
-
-// y^2 == x^3 + 3 over Fq for an affine canonical point (identity (0,0) accepted: G1P::in_curve)
-bool h_on_curve(const uint64_t* p) {
-  bool zero = true;
-  for (int i = 0; i < 8; ++i) zero = zero && p[i] == 0;
-  if (zero) return true;
-  const U256 x = u256_from_u64(p), y = u256_from_u64(p + 4);
-  if (Fq::geq_p(x) || Fq::geq_p(y)) return false;
-  const U256 xm = Fq::to_mont(x), ym = Fq::to_mont(y);
-  U256 three = u256_zero();
-  three.w[0] = 3;
-  const U256 rhs = Fq::add(Fq::mul(Fq::mul(xm, xm), xm), Fq::to_mont(three));
-  return Fq::eq(Fq::mul(ym, ym), rhs);
-}
-
-void h_neg_g1(const uint64_t* p, uint64_t* out) {
-  for (int i = 0; i < 8; ++i) out[i] = p[i];
-  const U256 y = u256_from_u64(p + 4);
-  if (Fq::is_zero(y)) return;
-  U256 q;
-  for (int i = 0; i < 8; ++i) q.w[i] = Bn254FqParams::P[i];
-  // q - y (y < q)
-  uint64_t borrow = 0;
-  U256 d;
-  for (int i = 0; i < 8; ++i) {
-    const uint64_t t = (uint64_t)q.w[i] - y.w[i] - borrow;
-    d.w[i] = (uint32_t)t;
-    borrow = (t >> 63) & 1;
-  }
-  u256_to_u64(d, out + 4);
-}
-
-}  // namespace
-
-static int verify_with_vk(pbf_ctx* ctx, size_t n, const U256& omega, const uint64_t (*pre)[8], const uint64_t* d_srs,
-                          const uint64_t* g2, const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* chal,
-                          const uint64_t* u_in, const uint64_t* k1k2, int mode, int* ok, hipStream_t s);
-
-// Plonk::verify (src/plonk.rs:468-650). srs: >= n affine G1 points (g1s, device), g2: [g2_1, g2_s]
-// (2 x 16 u64, host); proof as pbf_plonk_prove_bn254 returns it; u the verifier's random
-// scalar (rand[0], plonk.rs:519). mode 0 keeps step 7's t_z (plonk.rs:575-581, no alpha on
-// the permutation term), mode 1 the paper's. *ok = 1 iff e(E1, [s]G2) == e(E2, G2).
-extern "C" int pbf_plonk_verify_bn254_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
-                                          const uint64_t* d_srs, size_t srs_m, const uint64_t* g2,
-                                          const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* chal,
-                                          const uint64_t* u_in, const uint64_t* k1k2, int mode, int* ok, void* stream) {
-  if (!ctx || !d_q || !d_copies || !d_srs || !g2 || !proof_pts || !proof_f || !chal || !u_in || !k1k2 || !ok)
-    return fail(PBF_EINVAL, "null argument");
-  *ok = 0;
-  if (n < 8 || (n & (n - 1))) return fail(PBF_EINVAL, "n must be a power of two >= 8");
-  if (srs_m < n) return fail(PBF_EINVAL, "SRS too short");
-  PBF_HIP(hipSetDevice(ctx->device));
-  uint32_t log_n = 0;
-  while ((1ull << log_n) < n) ++log_n;
-  hipStream_t s = (hipStream_t)stream;
-  int rc;
-  // Step 1-2: proof points on the curve, proof fields canonical (plonk.rs:523-547)
-  for (int i = 0; i < 9; ++i)
-    if (!h_on_curve(proof_pts + 8 * i)) return 0;
-  for (int i = 0; i < 7; ++i)
-    if (Fr::geq_p(u256_from_u64(proof_f + 4 * i))) return 0;
-  const U256 omega = hroot(log_n);
-  uint64_t pre[8][8];
-  if ((rc = verifier_vk(ctx, n, omega, d_q, d_copies, d_srs, srs_m, k1k2, s, pre))) return rc;
-  return verify_with_vk(ctx, n, omega, pre, d_srs, g2, proof_pts, proof_f, chal, u_in, k1k2, mode, ok, s);
-}
-
-// Plonk::verify's preprocessing, shared by the single and the batched verifier
-// (verify_batch.hip): pre = the commitments of q_m q_l q_r q_o q_c s_sigma_1..3; omega =
-// fr_root_of_unity(log2 n).
-U256 pbf::fr_root_of_unity(uint32_t log_n) { return hroot(log_n); }
-
-int pbf::verifier_vk(pbf_ctx* ctx, size_t n, const U256& omega, const uint64_t* d_q, const uint64_t* d_copies,
-                     const uint64_t* d_srs, size_t srs_m, const uint64_t* k1k2, hipStream_t s, uint64_t pre[8][8]) {
-  const uint64_t E = 32;
-  int rc;
-  // preprocessing (plonk.rs:507-517): commitments of q_m q_l q_r q_o q_c, s_sigma_1..3 -- a
-  // verification key: kept in the context for this circuit and SRS (q, copies and the SRS
-  // compared with device copies of the ones it was built from on every call;
-  // PBF_VERIFIER_NO_VK=1 recomputes them, as the reference does)
-  const U256 one = fr_one_m();
-  const U256 k1 = hm(k1k2), k2 = hm(k1k2 + 4);
-  std::vector<uint64_t> vk_key;
-  const bool vk_on = ctx->options.num("verifier.vk", 1) != 0;
-  if (vk_on) {
-    const SnapItem items[3] = {{"q", d_q, 20 * (uint64_t)n},
-                               {"copies", d_copies, 6 * (uint64_t)n},
-                               {"g1pts", d_srs, 8 * (uint64_t)srs_m}};
-    bool same = false;
-    if ((rc = snapshot_check(ctx, "vk", items, 3, s, &same))) return rc;
-    if (!same) ctx->vk_key.clear();  // rebuilt below; valid again once complete
-    vk_key = {(uint64_t)n, (uint64_t)srs_m};
-    for (int i = 0; i < 8; ++i) vk_key.push_back(k1k2[i]);
-  }
-  if (vk_on && ctx->vk_key == vk_key && ctx->vk_pts.size() == 64) {
-    memcpy(pre, ctx->vk_pts.data(), 64 * sizeof(uint64_t));
-  } else {
-  DevBuf &hp = ctx->buf("vf.hpow"), &sg = ctx->buf("vf.sigma"), &cf = ctx->buf("vf.coef"), &fl = ctx->buf("vf.flag");
-  if ((rc = hp.ensure(n * E)) || (rc = sg.ensure(3 * n * E)) || (rc = cf.ensure(8 * n * E)) || (rc = fl.ensure(64)))
-    return rc;
-  uint64_t w_plain[4];
-  hout(w_plain, omega);
-  PBF_HIP(hipMemsetAsync(fl.p, 0, sizeof(int), s));
-  hipLaunchKernelGGL(k_powers29, dim3(blocks_for((n + PV_CHUNK - 1) / PV_CHUNK)), dim3(256), 0, s, (uint64_t*)hp.p,
-                     (uint64_t)n, powers_tab29(omega, one));
-  hipLaunchKernelGGL(k_sigma, dim3(blocks_for(3 * n)), dim3(256), 0, s, d_copies, (const uint64_t*)hp.p, (uint64_t)n,
-                     (uint64_t)0, (uint64_t)n, k1, k2, (uint64_t*)sg.p, (int*)fl.p);
-  PBF_HIP(hipGetLastError());
-  uint64_t* c = (uint64_t*)cf.p;
-  // slots: 0 q_m 1 q_l 2 q_r 3 q_o 4 q_c 5 s1 6 s2 7 s3  (q columns: q_l q_r q_o q_m q_c)
-  const int qcol[5] = {3, 0, 1, 2, 4};
-  for (int k = 0; k < 5; ++k)
-    PBF_HIP(hipMemcpyAsync(c + 4 * n * k, d_q + 4 * n * qcol[k], n * E, hipMemcpyDeviceToDevice, s));
-  PBF_HIP(hipMemcpyAsync(c + 4 * n * 5, sg.p, 3 * n * E, hipMemcpyDeviceToDevice, s));
-  if ((rc = pbf_ntt_fr256_batch_dev(ctx, w_plain, c, c, n, 8, 1, s))) return rc;
-  const Affine* tbl = nullptr;  // the SRS window table, when a prove on this context built it
-  if ((rc = msm_fixed_lookup(ctx, d_srs, srs_m, s, &tbl))) return rc;
-  if (tbl) {
-    DevBuf& vs = ctx->buf("vf.commits");
-    if ((rc = vs.ensure(8 * sizeof(Xyzz)))) return rc;
-    for (int k = 0; k < 8; ++k)
-      if ((rc = msm_fixed_device(ctx, tbl, srs_m, 0, c + 4 * n * k, n, s, (Xyzz*)vs.p + k))) return rc;
-    if ((rc = msm_fixed_wait(ctx, s))) return rc;
-    Xyzz h[8];
-    PBF_HIP(hipMemcpyAsync(h, vs.p, sizeof(h), hipMemcpyDeviceToHost, s));
-    PBF_HIP(hipStreamSynchronize(s));
-    for (int k = 0; k < 8; ++k) xyzz_to_affine_u64(h[k], pre[k]);
-  } else {
-    for (int k = 0; k < 8; ++k)
-      if ((rc = pbf_msm_g1_bn254_dev(ctx, d_srs, c + 4 * n * k, n, pre[k], s))) return rc;
-  }
-  int bad = 0;
-  PBF_HIP(hipMemcpyAsync(&bad, fl.p, sizeof(int), hipMemcpyDeviceToHost, s));
-  PBF_HIP(hipStreamSynchronize(s));
-  if (bad) return fail(PBF_EINVAL, "bad copy constraint label");
-  if (vk_on) {
-    ctx->vk_key = vk_key;
-    ctx->vk_pts.assign(&pre[0][0], &pre[0][0] + 64);
-  }
-  }
-  return 0;
-}
-
-// Plonk::verify steps 4-12 for one proof whose points and fields passed steps 1-2
-static int verify_with_vk(pbf_ctx* ctx, size_t n, const U256& omega, const uint64_t (*pre)[8], const uint64_t* d_srs,
-                          const uint64_t* g2, const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* chal,
-                          const uint64_t* u_in, const uint64_t* k1k2, int mode, int* ok, hipStream_t s) {
-  const U256 one = fr_one_m();
-  const U256 k1 = hm(k1k2), k2 = hm(k1k2 + 4);
-  int rc;
-  const U256 alpha = hm(chal), beta = hm(chal + 4), gamma = hm(chal + 8), zc = hm(chal + 12), v = hm(chal + 16);
-  const U256 u = hm(u_in);
-  const U256 a_z = hm(proof_f), b_z = hm(proof_f + 4), c_z = hm(proof_f + 8), s1_z = hm(proof_f + 12),
-             s2_z = hm(proof_f + 16), r_z = hm(proof_f + 20), zw_z = hm(proof_f + 24);
-  // Step 4-5: Z_H(z) = z^n - 1, L_1(z) = n^-1 sum_{i<n} z^i (the interpolated Lagrange poly)
-  const U256 zn = hpow64(zc, n);
-  const U256 z_h_z = Fr::sub(zn, one);
-  U256 l1 = u256_zero(), zp = one;
-  for (uint64_t i = 0; i < n && i < 64; ++i) { l1 = Fr::add(l1, zp); zp = Fr::mul(zp, zc); }
-  if (n > 64) {  // geometric sum (z^n - 1)/(z - 1) for z != 1
-    const U256 zm1 = Fr::sub(zc, one);
-    l1 = Fr::is_zero(zm1) ? hm64(n) : Fr::mul(z_h_z, hinvm(zm1));
-  }
-  l1 = Fr::mul(l1, hinvm(hm64(n)));
-  if (Fr::is_zero(z_h_z)) return 0;  // the reference's .unwrap() would panic (plonk.rs:581)
-  // Step 7: t_z
-  const U256 alpha2 = Fr::mul(alpha, alpha);
-  U256 perm = Fr::mul(Fr::mul(Fr::add(Fr::add(a_z, Fr::mul(beta, s1_z)), gamma),
-                              Fr::add(Fr::add(b_z, Fr::mul(beta, s2_z)), gamma)),
-                      Fr::mul(Fr::add(c_z, gamma), zw_z));
-  if (mode == 1) perm = Fr::mul(perm, alpha);
-  const U256 t_z = Fr::mul(Fr::sub(Fr::sub(r_z, perm), Fr::mul(l1, alpha2)), hinvm(z_h_z));
-  // Steps 8-10 as one linear combination of points (bases / scalars)
-  U256 vp[7];
-  vp[0] = one;
-  for (int i = 1; i < 7; ++i) vp[i] = Fr::mul(vp[i - 1], v);
-  const U256 d2 = Fr::add(Fr::add(Fr::mul(Fr::mul(Fr::mul(Fr::mul(Fr::mul(Fr::add(Fr::add(a_z, Fr::mul(beta, zc)), gamma),
-      Fr::add(Fr::add(b_z, Fr::mul(Fr::mul(beta, k1), zc)), gamma)), Fr::add(Fr::add(c_z, Fr::mul(Fr::mul(beta, k2), zc)), gamma)),
-      alpha), v), one), Fr::mul(Fr::mul(l1, alpha2), v)), u);
-  const U256 d3 = Fr::mul(Fr::mul(Fr::mul(Fr::mul(Fr::mul(Fr::add(Fr::add(a_z, Fr::mul(beta, s1_z)), gamma),
-      Fr::add(Fr::add(b_z, Fr::mul(beta, s2_z)), gamma)), alpha), v), beta), zw_z);
-  U256 ecoef = Fr::add(t_z, Fr::mul(v, r_z));
-  ecoef = Fr::add(ecoef, Fr::mul(vp[2], a_z));
-  ecoef = Fr::add(ecoef, Fr::mul(vp[3], b_z));
-  ecoef = Fr::add(ecoef, Fr::mul(vp[4], c_z));
-  ecoef = Fr::add(ecoef, Fr::mul(vp[5], s1_z));
-  ecoef = Fr::add(ecoef, Fr::mul(vp[6], s2_z));
-  ecoef = Fr::add(ecoef, Fr::mul(u, zw_z));
-  const U256 omega_m = omega;
-  // bases: proof a b c z t_lo t_mid t_hi w_z w_zw | q_m q_l q_r q_o q_c s1 s2 s3 | G
-  std::vector<uint64_t> bases(18 * 8), sc(18 * 4);
-  for (int i = 0; i < 9; ++i) memcpy(&bases[8 * i], proof_pts + 8 * i, 64);
-  for (int k = 0; k < 8; ++k) memcpy(&bases[8 * (9 + k)], pre[k], 64);
-  std::vector<uint64_t> g0(8);
-  PBF_HIP(hipMemcpyAsync(g0.data(), d_srs, 64, hipMemcpyDeviceToHost, s));
-  PBF_HIP(hipStreamSynchronize(s));
-  memcpy(&bases[8 * 17], g0.data(), 64);
-  U256 scal[18];
-  scal[0] = vp[2];                                       // a_s
-  scal[1] = vp[3];                                       // b_s
-  scal[2] = vp[4];                                       // c_s
-  scal[3] = d2;                                          // z_s
-  scal[4] = one;                                         // t_lo
-  scal[5] = hpow64(zc, n + 2);                           // t_mid
-  scal[6] = hpow64(zc, 2 * n + 4);                       // t_hi
-  scal[7] = zc;                                          // w_z * z
-  scal[8] = Fr::mul(Fr::mul(u, zc), omega_m);            // w_zw * u z w
-  scal[9] = Fr::mul(Fr::mul(a_z, b_z), v);               // q_m
-  scal[10] = Fr::mul(a_z, v);                            // q_l
-  scal[11] = Fr::mul(b_z, v);                            // q_r
-  scal[12] = Fr::mul(c_z, v);                            // q_o
-  scal[13] = v;                                          // q_c
-  scal[14] = vp[5];                                      // s1
-  scal[15] = vp[6];                                      // s2
-  scal[16] = Fr::sub(u256_zero(), d3);                   // - s3 d3
-  scal[17] = Fr::sub(u256_zero(), ecoef);                // - E
-  for (int i = 0; i < 18; ++i) hout(&sc[4 * i], scal[i]);
-  DevBuf &db = ctx->buf("vf.bases"), &ds = ctx->buf("vf.scalars");
-  if ((rc = db.ensure(18 * 64)) || (rc = ds.ensure(18 * 32))) return rc;
-  PBF_HIP(hipMemcpyAsync(db.p, bases.data(), 18 * 64, hipMemcpyHostToDevice, s));
-  PBF_HIP(hipMemcpyAsync(ds.p, sc.data(), 18 * 32, hipMemcpyHostToDevice, s));
-  uint64_t e2[8], e1[8];
-  if ((rc = pbf_msm_g1_bn254_dev(ctx, (const uint64_t*)db.p, (const uint64_t*)ds.p, 18, e2, s))) return rc;
-  // E1 = w_z + u w_zw
-  U256 one_u[2] = {one, u};
-  std::vector<uint64_t> sc1(8);
-  hout(&sc1[0], one_u[0]);
-  hout(&sc1[4], one_u[1]);
-  PBF_HIP(hipMemcpyAsync(db.p, proof_pts + 8 * 7, 2 * 64, hipMemcpyHostToDevice, s));
-  PBF_HIP(hipMemcpyAsync(ds.p, sc1.data(), 2 * 32, hipMemcpyHostToDevice, s));
-  if ((rc = pbf_msm_g1_bn254_dev(ctx, (const uint64_t*)db.p, (const uint64_t*)ds.p, 2, e1, s))) return rc;
-  // e(E1, [s]G2) == e(E2, G2)  <=>  e(E1, [s]G2) e(-E2, G2) == 1  (plonk.rs:646-650)
-  uint64_t g1s[16], g2s[32];
-  memcpy(g1s, e1, 64);
-  h_neg_g1(e2, g1s + 8);
-  memcpy(g2s, g2 + 16, 128);  // [s]G2
-  memcpy(g2s + 16, g2, 128);  // G2
-  return pairing_check_on_stream(ctx, g1s, g2s, 2, ok, s);
-}
-
-extern "C" int pbf_plonk_verify_bn254(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies,
-                                      const uint64_t* srs, size_t srs_m, const uint64_t* g2, const uint64_t* proof_pts,
-                                      const uint64_t* proof_f, const uint64_t* chal, const uint64_t* u,
-                                      const uint64_t* k1k2, int mode, int* ok) {
-  if (!ctx || !q || !copies || !srs) return fail(PBF_EINVAL, "null argument");
-  PBF_HIP(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->host_stream();
-  DevBuf &dq = ctx->buf("vf.q"), &dc = ctx->buf("vf.copies"), &dsrs = ctx->buf("vf.srs");
-  int rc;
-  if ((rc = dq.ensure(5 * n * 32)) || (rc = dc.ensure(3 * n * 16)) || (rc = dsrs.ensure(srs_m * 64))) return rc;
-  PBF_HIP(hipMemcpyAsync(dq.p, q, 5 * n * 32, hipMemcpyHostToDevice, s));
-  PBF_HIP(hipMemcpyAsync(dc.p, copies, 3 * n * 16, hipMemcpyHostToDevice, s));
-  PBF_HIP(hipMemcpyAsync(dsrs.p, srs, srs_m * 64, hipMemcpyHostToDevice, s));
-  return pbf_plonk_verify_bn254_dev(ctx, n, (const uint64_t*)dq.p, (const uint64_t*)dc.p, (const uint64_t*)dsrs.p,
-                                    srs_m, g2, proof_pts, proof_f, chal, u, k1k2, mode, ok, s);
 }
 
 // ---------------------------------------------------------------- synthetic config-5 inputs

@@ -1,7 +1,7 @@
 // Batched Plonk::verify over BN254 on gfx950: `count` proofs of one circuit, one 2-pair
 // pairing check (include/pbf.h pbf_plonk_verify_bn254_batch*).
 //
-// The single verifier (prover.hip "Plonk::verify") checks, per proof i,
+// The single verifier (verify.hip) checks, per proof i,
 //     e(E1_i, [s]G2) == e(E2_i, G2),   E1_i = W_z,i + u_i W_zw,i,   E2_i = sum_j scal_ij base_ij
 // with 18 bases: the proof's 9 points, the circuit's 8 preprocessed commitments and G. The
 // pairing is bilinear, so for caller-chosen weights rho_i
@@ -24,7 +24,7 @@
 #include <cstring>
 #include <vector>
 #include "../../include/pbf.h"
-#include "msm.hpp"
+#include "prover.hpp"
 
 using namespace pbf;
 
@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(256) k_vb_curve(const uint64_t* pts, uint32_t 
   if (bad) atomicOr(flag + i, 1);
 }
 
-// prover.hip steps 4-10 for proof i = one lane, every output times rho_i:
+// verify.hip steps 4-10 for proof i = one lane, every output times rho_i:
 //   sc[9 i + j]      j < 9: a b c z t_lo t_mid t_hi w_z w_zw
 //   e1s[E1_N i + E1_AT + 0, 1]  rho, rho u
 //   contrib[j][i]    j < 9: q_m q_l q_r q_o q_c s1 s2 (-d3 on s3) (-E on G)
@@ -223,21 +223,6 @@ __global__ void __launch_bounds__(64) k_vb_colsum2(const uint64_t* part, uint32_
   if (threadIdx.x == 0) u256_to_u64(acc, out + 4 * j);
 }
 
-// (x, q - y), the identity unchanged
-void neg_g1(const uint64_t* p, uint64_t* out) {
-  for (int i = 0; i < 8; ++i) out[i] = p[i];
-  const U256 y = u256_from_u64(p + 4);
-  if (Fq::is_zero(y)) return;
-  U256 d;
-  uint64_t borrow = 0;
-  for (int i = 0; i < 8; ++i) {
-    const uint64_t t = (uint64_t)Bn254FqParams::P[i] - y.w[i] - borrow;
-    d.w[i] = (uint32_t)t;
-    borrow = (t >> 63) & 1;
-  }
-  u256_to_u64(d, out + 4);
-}
-
 struct Batch {
   pbf_ctx* ctx;
   hipStream_t s;
@@ -300,10 +285,8 @@ struct Batch {
   }
 };
 
-bool fr_canonical(const uint64_t* p) { return !Fr::geq_p(u256_from_u64(p)); }
-
 // every argument error, before anything is enqueued. chal and u are taken as the single
-// verifier takes them (prover.hip hm()): any 256-bit value, reduced mod r.
+// verifier takes them (fr_host.hpp hm()): any 256-bit value, reduced mod r.
 int vb_validate(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies, const uint64_t* srs, size_t srs_m,
                 const uint64_t* g2, size_t count, const uint64_t* proof_pts, const uint64_t* proof_f,
                 const uint64_t* chal, const uint64_t* u, const uint64_t* rho, const uint64_t* k1k2, int* ok) {

@@ -91,6 +91,82 @@ def test_sharded_prove_virtual_ranks(G, log_n, mode):
     ctx0.close()
 
 
+def _prove_on_virtual_ranks(G, n, mode, inputs, options=None, proofs=2):
+    """`proofs` sharded proofs on each of G rank threads (own context with `options`, own stream).
+    Returns (out, refused, errs): the proofs per rank, the PbfError text of a rank whose prove was
+    refused, and anything else that went wrong. No thread is left waiting: an unexpected exception
+    aborts the group's barrier, and the joins time out."""
+    import torch
+
+    import pbf
+    from multigpu import LocalComm, LocalGroup, ShardedProver
+
+    dq, dc, dabc, dsrs, srs_m, chal, rnd = inputs
+    group = LocalGroup(G)
+    out, refused, errs = [None] * G, [None] * G, []
+
+    def rank_main(r):
+        try:
+            c = pbf.Context(0, options=options)
+            st = torch.cuda.Stream()
+            with torch.cuda.stream(st):
+                sp = ShardedProver(c, LocalComm(group, r), r, G, n, stream=st.cuda_stream)
+                try:
+                    out[r] = [sp.prove(dq.data_ptr(), dc.data_ptr(), dabc.data_ptr(), chal, rnd, dsrs.data_ptr(), srs_m,
+                                       mode=mode) for _ in range(proofs)]
+                except pbf.PbfError as e:
+                    refused[r] = str(e)
+            st.synchronize()
+            c.close()
+        except Exception as e:  # reported by the main thread
+            errs.append(f"rank {r}: {e!r}")
+            group.barrier.abort()
+
+    ts = [threading.Thread(target=rank_main, args=(r,)) for r in range(G)]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join(timeout=240)
+    assert not any(t.is_alive() for t in ts), "rank hung"
+    return out, refused, errs
+
+
+@pytest.mark.parametrize("G,log_n,mode", [(2, 6, 1), (2, 6, 0), (4, 6, 1), (8, 6, 1)])
+def test_sharded_prove_without_proving_key(G, log_n, mode):
+    """Option prover.pk = 0: every proof rebuilds the circuit polynomials, in the slot layout of
+    its own that the sharded prover keeps for this case (the coset slots after a b c z z(w x), the
+    11 coefficient slots in the scratch buffer). n = 64 = G^2 is the smallest n for G = 8."""
+    n = 1 << log_n
+    ctx0, inputs, (pts0, fs0) = _inputs(n, 0x5EED0105 + log_n, mode)
+    out, refused, errs = _prove_on_virtual_ranks(G, n, mode, inputs, options={"prover.pk": 0})
+    assert not errs, errs
+    assert refused == [None] * G, refused
+    for r in range(G):
+        for k, (pts, fs) in enumerate(out[r]):
+            assert np.array_equal(pts, pts0) and np.array_equal(fs, fs0), f"rank {r} proof {k} differs from one GPU's"
+    ctx0.close()
+
+
+def test_sharded_prove_refuses_an_unsatisfied_circuit_on_every_rank():
+    """One witness row spoiled among rank 1's rows only: rank 0's rows satisfy their gates, yet
+    both ranks must refuse (the flags are all-gathered), so neither waits for the other in a
+    later collective."""
+    import torch
+
+    G, n = 2, 64
+    ctx0, (dq, dc, dabc, dsrs, srs_m, chal, rnd), _ = _inputs(n, 0x5EED0205, 1)
+    bad = dabc.clone()
+    row = n // G + 7                  # rank 1 holds rows [n / G, n)
+    bad[4 * (2 * n + row)] ^= 1       # c of that row: its gate a b = c no longer holds
+    torch.cuda.synchronize()
+    out, refused, errs = _prove_on_virtual_ranks(G, n, 1, (dq, dc, bad, dsrs, srs_m, chal, rnd), proofs=1)
+    assert not errs, errs
+    for r in range(G):
+        assert out[r] is None and refused[r] is not None, f"rank {r} was not refused"
+        assert "constraints not satisfied" in refused[r], refused[r]
+    ctx0.close()
+
+
 @pytest.mark.parametrize("G", [2, 4])
 def test_sharded_prove_on_a_non_current_stream(G):
     """pbf.h: the comm callbacks are ordered on the stream the library passes, which need not
