@@ -110,6 +110,9 @@ struct NttPlan {
   // (A: R x W, B: Ns/W x R; null when unused), W = tws_w columns per tile
   std::shared_ptr<DevBuf> tws_a, tws_b;
   int tws_w = 0;
+  // forward "10,10" plans: the second pass's [r][k] table in the order of the tile-major
+  // intermediate (ntt_launch.hip pass_tab_blocked, gl_blocked); empty for every other plan
+  DevBuf post_blk;
   // regrouped 2^24 plan (ntt_gl.hpp ntt_gl_rg2_kernel): 8,8,8 passes with the general
   // twiddles between 64-point blocks only; tables tc1[a2l][r2][k1] (4096), t2[a1][K] (2^18),
   // and the last pass's geometric factors C[r2][X], D[X] (X < 2^18, n^-1 folded into C for the

@@ -55,6 +55,10 @@ struct GlPassArgs {
   // second pass skips its own (skip_pass_tw)
   const uint64_t* post_tw;
   uint32_t skip_pass_tw;
+  // SP 2 (both passes of a "10,10" plan): the intermediate is tile-major, Yb[k >> 3][j][k & 7]
+  // for the first pass's output y(j, k), one second-pass tile (8 columns k x 1024 rows j) per
+  // contiguous block, blk_pitch elements from one block to the next; post_tw is in that order
+  uint64_t blk_pitch;
   // coset variants (template parameter CS of the kernel). CS 1, the first pass
   // of a forward transform: polynomial `poly` is the cs_len coefficients at in + poly*in_pitch
   // (in_pitch = cs_len), element i loads times shift^i, and i >= cs_len is zero padding that is
@@ -218,23 +222,35 @@ __device__ __forceinline__ uint64_t gl_cs_factor(const GlPassArgs& a, uint64_t i
 
 constexpr int GL_STORES = 16;  // global stores per thread per tile (NSUB_C * C)
 
+// The tile-major intermediate of SP 2: elements from one 8192-element block to the next. A pad
+// that takes the 128 blocks a first-pass tile writes off the 64-KiB stride measured no faster
+// (DESIGN.md §3.1 round 9), so the blocks are dense; a multiple of 2 keeps the 16-B loads aligned.
+constexpr uint64_t GL_BLK_PITCH = 8192;
+static_assert(GL_BLK_PITCH >= 8192 && GL_BLK_PITCH % 2 == 0, "block pitch");
+typedef uint64_t gl_u64x2 __attribute__((ext_vector_type(2)));
+
 // One tile: stages A, B, C and the stores.
 // RG (regrouped 2^24 plan, ntt_gl_rg2_kernel below): 1 = its first pass, 3 = its last pass.
 // CS (coset transforms): 1 = a first pass that scales its loads by shift^i and reads no zero
 // padding, 2 = a last pass that scales its stores by shift^-k n^-1 (GlPassArgs cs_*).
 // SP (the second pass of a plain forward two-pass plan, run_gl_group): the pass compiled with
 // only what such a plan executes: no pass-twiddle code (the first pass applied it: post_tw),
-// no scaled table and no split store. 1 = log_ns from the arguments, 2 = log_ns = LOGR (both
-// passes of one radix: the index arithmetic of the stores folds to constants). 0 = the generic
+// no scaled table and no split store. 1 = log_ns from the arguments. 0 = the generic
 // kernel of every other pass and plan. (The first pass with post_tw unconditional measured
 // no faster and 5.6 VALU per element more, DESIGN.md §3.1 round 7: it stays generic.)
+// 2 = both passes of one radix 2^10 ("10,10"), FIRST or not, with the intermediate between them
+// tile-major (GlPassArgs blk_pitch): the first pass's stage C takes 8 digits x 8 columns per
+// wave, so that each of its wave stores (and post_tw loads) is the 512 contiguous bytes of one
+// block; the second pass reads its tile as 64 contiguous KiB, 16 B per lane and load, and its
+// log_ns is the constant LOGR (the index arithmetic of its stores folds to constants).
 template <int LOGR, int E64, bool FIRST, int TILE, int RG = 0, int CS = 0, int SP = 0>
 __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint32_t tile, uint32_t tiles, int t) {
   using Sh = GlShape<LOGR, TILE>;
   constexpr int C = Sh::C, LOGC = Sh::LOGC, W = Sh::W, NT = Sh::NT, YP = Sh::YP;
   (void)YP;
   static_assert(Sh::NSUB_C * C == GL_STORES, "stores per thread");
-  static_assert(SP == 0 || (!FIRST && RG == 0 && CS == 0 && SP <= 2), "SP: second pass of a plain two-pass plan");
+  static_assert(SP == 0 || ((!FIRST || SP == 2) && RG == 0 && CS == 0 && SP <= 2), "SP: plain two-pass plan");
+  static_assert(SP != 2 || (LOGR == 10 && TILE == 8192), "SP 2: the 10,10 plan");
   static_assert(RG == 0 || (LOGR == 8 && TILE == 4096 && FIRST == (RG == 1)), "RG shape");
   static_assert(CS == 0 || (FIRST == (CS == 1) && (RG == 0 || RG == 2 * CS - 1)), "CS 1: first pass, CS 2: last pass");
   const FieldArgs f{};
@@ -244,10 +260,23 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
   const uint64_t j0 = (uint64_t)kb * W;
   const uint64_t* in = a.in + (uint64_t)poly * a.in_pitch;
   const uint64_t stride = a.n >> LOGR;  // input rows (r) are n/R long
+  constexpr bool BLK_IN = SP == 2 && !FIRST, BLK_OUT = SP == 2 && FIRST;
 
   // ---------------- stage A: load, pass twiddle, 4-point DFTs over s1
   uint64_t v[16];
-  if constexpr (CS == 1) {
+  if constexpr (BLK_IN) {
+    // the tile is block kb, element (r, w) at r*W + w: thread t takes the pairs 2t + 1024 u'
+    // (u' < 8), i.e. rows r = 128 u' + (t >> 2) = 256 s1 + 16 s2 + r2 with s1 = u' >> 1,
+    // s2 = 8 (u' & 1) + (t >> 6), r2 = (t >> 2) & 15, and columns w = 2 (t & 3) + b: v[(2h + b)*4
+    // + s1], h = u' & 1, so that each group of four shares (s2, r2, w) like the natural mapping
+    const gl_u64x2* blk = (const gl_u64x2*)(in + (uint64_t)kb * a.blk_pitch) + t;
+#pragma unroll
+    for (int up = 0; up < 8; ++up) {
+      const gl_u64x2 e = blk[512 * up];
+      v[(2 * (up & 1)) * 4 + (up >> 1)] = e.x;
+      v[(2 * (up & 1) + 1) * 4 + (up >> 1)] = e.y;
+    }
+  } else if constexpr (CS == 1) {
     // in groups of 8 elements like the pass twiddle below: a group's data and factor loads
     // issue together; an element past the coefficients is 0 and loads neither
 #pragma unroll
@@ -322,12 +351,27 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
   }
 #pragma unroll
   for (int u = 0; u < 4; ++u) dft_reg<G, 2, sub_root_exp(E64, 2)>(v + u * 4, nullptr, f);
+  if constexpr (BLK_IN) {
+    // rw = r2*W + w = 2 (t & 63) + b: the two columns of a pair are neighbours in Z
 #pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int idx = t + NT * u;  // = s2*(C*W) + (r2*W + w)
-    const int s2 = idx / (C * W), rw = idx % (C * W);
+    for (int h = 0; h < 2; ++h) {
+      const int s2 = 8 * h + (t >> 6);
 #pragma unroll
-    for (int q1 = 0; q1 < 4; ++q1) lds[(q1 * 16 + s2) * (C * W) + rw] = v[u * 4 + bitrev_c(q1, 2)];
+      for (int q1 = 0; q1 < 4; ++q1) {
+        gl_u64x2 e;
+        e.x = v[(2 * h) * 4 + bitrev_c(q1, 2)];
+        e.y = v[(2 * h + 1) * 4 + bitrev_c(q1, 2)];
+        *(gl_u64x2*)(lds + (q1 * 16 + s2) * (C * W) + 2 * (t & 63)) = e;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int idx = t + NT * u;  // = s2*(C*W) + (r2*W + w)
+      const int s2 = idx / (C * W), rw = idx % (C * W);
+#pragma unroll
+      for (int q1 = 0; q1 < 4; ++q1) lds[(q1 * 16 + s2) * (C * W) + rw] = v[u * 4 + bitrev_c(q1, 2)];
+    }
   }
   __syncthreads();
 
@@ -370,10 +414,16 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
 
   // ---------------- stage C: table twiddle w_R^(r2*k1); C-point DFT over r2
   // sub-DFT (k1, w) of thread t: FIRST pass all 64 k1 of one column per wave (512-B runs
-  // of k in the output rows out[j*R + k]); later passes w fastest (W-element runs of j)
+  // of k in the output rows out[j*R + k]); later passes w fastest (W-element runs of j);
+  // tile-major stores: 8 digits k1 = 8 wave + (lane & 7) of all 8 columns per wave (the 64
+  // elements [j][k & 7] of this tile in block (k >> 3) = wave + 8 k2; the Y reads are a
+  // permutation of the 512-B span of those 8 k1: w ^ ysw(k1) runs over all 8 columns)
   auto c_map = [&](int u, int* k1, int* w) {
     const int idx = t + NT * u;
-    if constexpr (FIRST) {
+    if constexpr (BLK_OUT) {
+      *k1 = 8 * (t >> 6) + (t & 7);
+      *w = (t >> 3) & 7;
+    } else if constexpr (FIRST) {
       *k1 = idx & 63;
       *w = idx >> 6;
     } else {
@@ -439,7 +489,22 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
   }
 
   // ---------------- store
-  if constexpr (FIRST) {
+  if constexpr (BLK_OUT) {
+    // element and post_tw entry (block wave + 8 k2, [j0 + w][k1 & 7]): a wave-uniform base plus
+    // the lane
+    static_assert(Sh::NSUB_C == 1 && W == 8, "tile-major stores: one sub-DFT per thread");
+    const uint64_t base = (uint64_t)__builtin_amdgcn_readfirstlane(t >> 6) * a.blk_pitch + j0 * W;
+    const uint32_t lane = t & 63;
+    const uint64_t* ptw = a.post_tw + base;
+    uint64_t* o = a.out + (uint64_t)poly * a.out_pitch + base;
+    uint64_t tw[C];
+#pragma unroll
+    for (int k2 = 0; k2 < C; ++k2) tw[k2] = ptw[(uint64_t)(8 * k2) * a.blk_pitch + lane];
+#pragma unroll
+    for (int k2 = 0; k2 < C; ++k2) x[bitrev_c(k2, LOGC)] = G::mul(x[bitrev_c(k2, LOGC)], tw[k2], f);
+#pragma unroll
+    for (int k2 = 0; k2 < C; ++k2) o[(uint64_t)(8 * k2) * a.blk_pitch + lane] = x[bitrev_c(k2, LOGC)];
+  } else if constexpr (FIRST) {
     uint64_t* o = a.out + (uint64_t)poly * a.out_pitch;
 #pragma unroll
     for (int u = 0; u < Sh::NSUB_C; ++u) {

@@ -96,6 +96,19 @@ static Table pass_tab(uint64_t w_p, uint64_t R, uint64_t ns, uint64_t m) {
   return t;
 }
 
+// The [r][k] table of the second pass of a 2^10 x 2^10 plan (pass_tab(w, 1024, 1024): entry
+// w^(j k) for the first pass's output y(j, k)) in the order of the tile-major intermediate
+// (ntt_gl.hpp SP 2): entry (j, k) at (k >> 3) * pitch + j * 8 + (k & 7), so that the first pass's
+// store index is its table index. The pad of a block (pitch > 8192) is never read.
+static Table pass_tab_blocked(uint64_t w, uint64_t pitch, uint64_t m) {
+  Table t(128 * pitch, 0);
+  for (uint64_t k = 0; k < 1024; ++k) {
+    const Table col = geometric(1, hpow(w, k, m), 1024, m);
+    for (uint64_t j = 0; j < 1024; ++j) t[(k >> 3) * pitch + j * 8 + (k & 7)] = col[j];
+  }
+  return t;
+}
+
 // The same twiddles split for a last pass: w_p^(r k) = B[kb][r] * A[r][c] for k = kb W + c, with
 // A[r][c] = w_p^(r c) (R x W) and B[kb][r] = w_p^(r kb W) (ns/W x R)
 static std::pair<Table, Table> split_tabs(uint64_t w_p, uint64_t R, uint64_t W, uint64_t ns, uint64_t m) {
@@ -205,6 +218,12 @@ int make_plan(uint64_t m, uint64_t omega, uint64_t n, int inverse, NttPlan* p) {
     }
     ns *= R;
   }
+  // forward "10,10" plans keep their intermediate tile-major (gl_blocked): the second pass's
+  // table once more, in that order, for the first pass's stores. twpass[1] stays: the split-store
+  // and coset runs of this plan read it.
+  if (p->gl && !inverse && p->e64 == 39 && p->logr == std::vector<int>{10, 10} && p->twpass[1]->p &&
+      (rc = upload(p->post_blk, pass_tab_blocked(w, GL_BLK_PITCH, m))))
+    return rc;
   for (size_t i = 0; i < P; ++i) {
     const uint64_t R = 1ull << p->logr[i], w_r = hpow(w, n / R, m);
     auto b = std::make_shared<DevBuf>();
@@ -370,13 +389,24 @@ struct GlPassDesc {
   bool first;
   int rg;  // regrouped 2^24 plan: pass 1, 2 (ntt_gl_rg2_kernel) or 3; 0 = not regrouped
   int cs;  // coset variant: 1 = scales its loads, 2 = scales its stores
-  int sp;  // specialised second pass of a plain forward two-pass plan: 1, or 2 for equal radices
+  int sp;  // plain forward two-pass plan: 1 = its specialised second pass; 2 = either pass of "10,10"
 };
 
 // Two-pass plans apply the second pass's twiddle w^(j k) at the first pass's stores (post_tw,
 // gl_pass_args), when that pass has its [r][k] table and stores no split layout
 static bool two_pass_tw(const NttPlan& p, uint32_t split_log) {
   return p.logr.size() == 2 && split_log == 0 && p.twpass[1]->p;
+}
+
+// Plain forward "10,10" runs keep the intermediate between their passes tile-major (ntt_gl.hpp
+// SP 2): both passes are the SP 2 pair, the scratch takes gl_scratch_pitch per polynomial
+static bool gl_blocked(const NttPlan& p, bool coset, uint32_t split_log) {
+  return two_pass_tw(p, split_log) && !coset && p.post_blk.p != nullptr;
+}
+
+// Elements of intermediate scratch per polynomial
+static uint64_t gl_scratch_pitch(const NttPlan& p, bool coset, uint32_t split_log) {
+  return gl_blocked(p, coset, split_log) ? 128 * GL_BLK_PITCH : p.n;
 }
 
 static GlPassDesc gl_pass_desc(const NttPlan& p, size_t i, bool coset, uint32_t split_log) {
@@ -387,11 +417,11 @@ static GlPassDesc gl_pass_desc(const NttPlan& p, size_t i, bool coset, uint32_t 
   // coset: a forward transform's first pass scales its loads, an inverse's last pass its stores
   if (coset && !p.inverse && i == 0) d.cs = 1;
   if (coset && p.inverse && i == P - 1) d.cs = 2;
-  // plain forward two-pass plans whose second pass is radix 2^10 (the 2^20 default "10,10") and
-  // skips its twiddle: that pass compiled with only what such a plan executes (ntt_gl.hpp SP);
-  // instantiated for the forward standard root only. Equal radices: its log_ns is the constant 10.
-  if (two_pass_tw(p, split_log) && i == 1 && !coset && !p.inverse && p.e64 == 39 && d.logr == 10)
-    d.sp = p.logr[0] == 10 ? 2 : 1;
+  // plain forward two-pass plans whose second pass is radix 2^10 and skips its twiddle: that
+  // pass compiled with only what such a plan executes (ntt_gl.hpp SP); instantiated for the
+  // forward standard root only. Both passes of the 2^20 default "10,10": the tile-major pair.
+  if (gl_blocked(p, coset, split_log)) d.sp = 2;
+  else if (two_pass_tw(p, split_log) && i == 1 && !coset && !p.inverse && p.e64 == 39 && d.logr == 10) d.sp = 1;
   return d;
 }
 
@@ -410,7 +440,7 @@ static GlPassFn gl_kernel_e(const GlPassDesc& d) {
   if (d.rg == 3) return d.cs ? ntt_gl_pass_kernel<8, E, false, 4096, 3, 2> : ntt_gl_pass_kernel<8, E, false, 4096, 3>;
   if constexpr (E == 39) {
     if (d.sp == 1) return ntt_gl_pass_kernel<10, E, false, 8192, 0, 0, 1>;
-    if (d.sp == 2) return ntt_gl_pass_kernel<10, E, false, 8192, 0, 0, 2>;
+    if (d.sp == 2) return d.first ? ntt_gl_pass_kernel<10, E, true, 8192, 0, 0, 2> : ntt_gl_pass_kernel<10, E, false, 8192, 0, 0, 2>;
   }
   switch (d.logr) {
     case 6: return gl_kernel_lr<E, 6>(d);
@@ -509,7 +539,7 @@ static int run_gl_passes(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out
     const size_t b = batch - g0 < G ? batch - g0 : G;
     // scratch ring: one slot of G polynomials per stream (a stream's groups are serialised)
     const int rc = run_gl_group(p, d_in + g0 * in_pitch, d_out + g0 * p.n, b, s0, s1, sts[gi % ns], 0,
-                                (size_t)(gi % ns) * G * p.n, cs);
+                                (size_t)(gi % ns) * G * gl_scratch_pitch(p, cs != nullptr, split_log), cs);
     if (rc) return rc;
   }
   for (int i = 1; i < ns; ++i) {
@@ -599,6 +629,20 @@ static GlPassArgs gl_pass_args(const NttPlan& p, size_t i, const GlPassDesc& d, 
     else a.skip_pass_tw = 1;
   }
   if (a.post_tw && batch > 1 && tiles % 8 == 0) a.xcd_kmajor = 1;
+  a.blk_pitch = 0;
+  if (d.sp == 2) {
+    a.blk_pitch = GL_BLK_PITCH;
+    if (i == 0) {
+      a.post_tw = (const uint64_t*)p.post_blk.p;
+      a.out_pitch = 128 * GL_BLK_PITCH;
+    } else {
+      // the second pass reads no table, so k-major buys nothing, and its tiles lie one after
+      // another: linear order, neighbouring workgroups on neighbouring blocks (round 9: 0.2994
+      // against 0.3022 ms k-major at steady clocks, XCD-blocked 0.3033)
+      a.in_pitch = 128 * GL_BLK_PITCH;
+      a.xcd_kmajor = 0;
+    }
+  }
   a.cs_tab = a.cs_tab1 = nullptr;
   a.cs_bits = 0;
   a.cs_len = 0;
@@ -673,7 +717,8 @@ static int run_plan_impl(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out
     return 0;
   }
   const size_t P = p.logr.size();
-  const size_t bytes = (p.gl ? gl_scratch_polys(p, batch, split_log, fork) : batch) * p.n * 8;
+  const size_t bytes = p.gl ? gl_scratch_polys(p, batch, split_log, fork) * gl_scratch_pitch(p, cs != nullptr, split_log) * 8
+                            : batch * p.n * 8;
   int rc = s0.ensure(bytes);
   if (!rc && P > 2) rc = s1.ensure(bytes);
   if (rc) return rc;

@@ -8,12 +8,15 @@
 //              output digits), one scratch S: in->S, S->S, S->out (the last pass writes the
 //              natural-order output)
 //   inplace4   the same with 4 radix-2^6 passes (512-B runs everywhere)
+//   blocked2   2^20 x 32 only (round 9): stockham2 with the intermediate tile-major, every
+//              second-pass tile one contiguous block, dense or with a padded block pitch
 // each per polynomial (chain of one polynomial, then the next: its scratch can stay in the
 // 256 MiB Infinity Cache) or batched (every pass over both polynomials).
 // Build: hipcc -O3 --offload-arch=gfx950 ntt_floor.hip -o ntt_floor
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 struct Side {
@@ -26,8 +29,8 @@ struct Pass {
   uint64_t* out;
   uint32_t A;  // tile t -> (a, b) = (t % A, t / A)
   uint32_t tiles;  // per polynomial
-  uint32_t polys;  // polynomials per launch, `pstride` elements apart
-  uint64_t pstride;
+  uint32_t polys;  // polynomials per launch, `ps_in` / `ps_out` elements apart on either side
+  uint64_t ps_in, ps_out;
   Side si, so;
   int nt_in, nt_out, xcd;
 };
@@ -42,7 +45,7 @@ __global__ void __launch_bounds__(NT) k_move(Pass p) {
   const uint64_t poly = t / p.tiles;
   t %= p.tiles;
   const uint64_t a = t % p.A, b = t / p.A;
-  const uint64_t bi = a * p.si.ia + b * p.si.ib + poly * p.pstride, bo = a * p.so.ia + b * p.so.ib + poly * p.pstride;
+  const uint64_t bi = a * p.si.ia + b * p.si.ib + poly * p.ps_in, bo = a * p.so.ia + b * p.so.ib + poly * p.ps_out;
   const uint32_t mi = (1u << p.si.run_log) - 1, mo = (1u << p.so.run_log) - 1;
   uint64_t v[PER];
 #pragma unroll
@@ -78,7 +81,7 @@ static const uint64_t N = 1ull << 24;
 static Pass mk(const uint64_t* in, uint64_t* out, uint32_t A, uint32_t tiles, Side si, Side so) {
   Pass p;
   p.in = in; p.out = out; p.A = A; p.tiles = tiles; p.si = si; p.so = so;
-  p.nt_in = p.nt_out = 0; p.xcd = 0; p.polys = 1; p.pstride = 0;
+  p.nt_in = p.nt_out = 0; p.xcd = 0; p.polys = 1; p.ps_in = p.ps_out = 0;
   return p;
 }
 
@@ -114,9 +117,9 @@ static std::vector<Pass> inplace2(const uint64_t* in, uint64_t* S, uint64_t* out
 static uint64_t g_limit = 0;  // elements in every buffer
 // every term of an address grows with a, b, the row and the offset, so the last tile's last
 // element bounds them all: refuse a pass that could leave the buffers
-static uint64_t max_addr(const Pass& p, const Side& sd) {
+static uint64_t max_addr(const Pass& p, const Side& sd, uint64_t pstride) {
   const uint64_t a = p.A - 1, b = p.tiles / p.A - 1, e = TILE - 1;
-  return (p.polys - 1) * p.pstride + a * sd.ia + b * sd.ib + (e >> sd.run_log) * sd.rs + (e & ((1u << sd.run_log) - 1));
+  return (p.polys - 1) * pstride + a * sd.ia + b * sd.ib + (e >> sd.run_log) * sd.rs + (e & ((1u << sd.run_log) - 1));
 }
 static const uint64_t* g_bufs[4];
 static bool inside(const uint64_t* ptr, uint64_t last) {
@@ -125,7 +128,7 @@ static bool inside(const uint64_t* ptr, uint64_t last) {
   return false;
 }
 static void launch(const Pass& p) {
-  if (p.tiles % p.A || !inside(p.in, max_addr(p, p.si)) || !inside(p.out, max_addr(p, p.so))) {
+  if (p.tiles % p.A || !inside(p.in, max_addr(p, p.si, p.ps_in)) || !inside(p.out, max_addr(p, p.so, p.ps_out))) {
     fprintf(stderr, "pass out of bounds (tiles %u A %u): refusing to launch\n", p.tiles, p.A);
     exit(2);
   }
@@ -134,7 +137,7 @@ static void launch(const Pass& p) {
 
 // 2^20-point transforms (x = x0 + 2^10 x1), W-column tiles, over `polys` polynomials per launch
 static std::vector<Pass> batched(std::vector<Pass> v, uint32_t polys, uint64_t n) {
-  for (auto& p : v) { p.polys = polys; p.pstride = n; }
+  for (auto& p : v) { p.polys = polys; p.ps_in = p.ps_out = n; }
   return v;
 }
 static std::vector<Pass> stockham2_20(const uint64_t* in, uint64_t* s0, uint64_t* out, uint32_t wlog) {
@@ -151,6 +154,21 @@ static std::vector<Pass> inplace2_20(const uint64_t* in, uint64_t* S, uint64_t* 
   // P1 over x1 in place; P2 over x0: contiguous rows (k0 block) -> natural order X[k0 + 2^10 k1]
   return {mk(in, S, groups, 256, {W, q, wlog, 1024}, {W, q, wlog, 1024}),
           mk(S, out, groups, 256, {(uint64_t)W * 1024, rows, 12 - wlog, 1024}, {W, q, wlog, 1024})};
+}
+
+// stockham2 with the intermediate tile-major (round 9): y(j, k) at Yb[k >> 3][j][k & 7], every
+// second-pass tile of 8 columns x 1024 rows one contiguous block `pitch` elements after the last
+// (pitch = 8192 + pad). P1 writes 64-element (512-B) runs `pitch` apart, P2 reads 4096 contiguous
+// elements (half a block per 4096-element tile here) and writes the natural order as before. A
+// polynomial of the intermediate takes 128 * pitch elements.
+static std::vector<Pass> blocked2_20(const uint64_t* in, uint64_t* s0, uint64_t* out, uint32_t polys, uint64_t pad) {
+  const uint32_t W = 8, rows = 512, groups = 128;
+  const uint64_t n = 1ull << 20, q = (uint64_t)rows * 1024, pitch = 8192 + pad;
+  std::vector<Pass> v = {mk(in, s0, groups, 256, {W, q, 3, 1024}, {64, 64 * pitch, 6, pitch}),
+                         mk(s0, out, groups, 256, {pitch, 4096, 12, 0}, {W, q, 3, 1024})};
+  for (auto& p : v) { p.polys = polys; p.ps_in = p.ps_out = n; }
+  v[0].ps_out = v[1].ps_in = 128 * pitch;
+  return v;
 }
 
 struct Sched {
@@ -203,13 +221,16 @@ static Sched with(Sched s, int nt_in, int nt_out, int xcd, const char* name) {
   return s;
 }
 
-int main() {
+// ntt_floor        every schedule
+// ntt_floor p20    only the 2^20 x 32 schedules (after the same warm-up)
+int main(int argc, char** argv) {
+  const bool only20 = argc > 1 && !strcmp(argv[1], "p20");
   uint64_t *in, *out, *s0, *s1;
-  hipMalloc(&in, 2 * N * 8);
-  hipMalloc(&out, 2 * N * 8);
-  hipMalloc(&s0, 2 * N * 8);
-  hipMalloc(&s1, 2 * N * 8);
-  g_limit = 2 * N;
+  g_limit = 2 * N + (1ull << 20);  // slack: the padded tile-major intermediate of 32 polynomials
+  hipMalloc(&in, g_limit * 8);
+  hipMalloc(&out, g_limit * 8);
+  hipMalloc(&s0, g_limit * 8);
+  hipMalloc(&s1, g_limit * 8);
   g_bufs[0] = in; g_bufs[1] = out; g_bufs[2] = s0; g_bufs[3] = s1;
   hipMemset(in, 1, 2 * N * 8);
   hipMemset(s0, 0, 2 * N * 8);
@@ -224,26 +245,28 @@ int main() {
     hipDeviceSynchronize();
     timeit(Sched{"copy (contiguous, both polynomials)", {{c}}});
   }
-  Sched st{"stockham3 per polynomial", {stockham3(in, s0, s1, out), stockham3(in + N, s0 + N, s1 + N, out + N)}};
-  timeit(st);
-  Sched i3p{"inplace3 per polynomial (one 128 MiB S)", {inplace3(in, s0, out), inplace3(in + N, s0, out + N)}};
-  timeit(i3p);
-  timeit(with(i3p, 1, 1, 0, "inplace3 per polynomial, nt in/out"));
-  timeit(with(i3p, 0, 0, 1, "inplace3 per polynomial, XCD tile ranges"));
-  Sched i3b{"inplace3 two S (no reuse)", {inplace3(in, s0, out), inplace3(in + N, s0 + N, out + N)}};
-  timeit(i3b);
-  Sched i4p{"inplace4 per polynomial (one 128 MiB S)", {inplace4(in, s0, out), inplace4(in + N, s0, out + N)}};
-  timeit(i4p);
-  timeit(with(i4p, 1, 1, 0, "inplace4 per polynomial, nt in/out"));
-  timeit(with(i4p, 0, 0, 1, "inplace4 per polynomial, XCD tile ranges"));
-  timeit(with(i4p, 1, 1, 1, "inplace4 per polynomial, nt + XCD"));
-  for (uint32_t wl : {2u, 3u}) {
-    char nm[96];
-    snprintf(nm, sizeof nm, "inplace2 W=%u per polynomial", 1u << wl);
-    Sched i2{nm, {inplace2(in, s0, out, wl), inplace2(in + N, s0, out + N, wl)}};
-    timeit(i2);
-    snprintf(nm, sizeof nm, "inplace2 W=%u per polynomial, XCD tile ranges", 1u << wl);
-    timeit(with(i2, 0, 0, 1, nm));
+  if (!only20) {
+    Sched st{"stockham3 per polynomial", {stockham3(in, s0, s1, out), stockham3(in + N, s0 + N, s1 + N, out + N)}};
+    timeit(st);
+    Sched i3p{"inplace3 per polynomial (one 128 MiB S)", {inplace3(in, s0, out), inplace3(in + N, s0, out + N)}};
+    timeit(i3p);
+    timeit(with(i3p, 1, 1, 0, "inplace3 per polynomial, nt in/out"));
+    timeit(with(i3p, 0, 0, 1, "inplace3 per polynomial, XCD tile ranges"));
+    Sched i3b{"inplace3 two S (no reuse)", {inplace3(in, s0, out), inplace3(in + N, s0 + N, out + N)}};
+    timeit(i3b);
+    Sched i4p{"inplace4 per polynomial (one 128 MiB S)", {inplace4(in, s0, out), inplace4(in + N, s0, out + N)}};
+    timeit(i4p);
+    timeit(with(i4p, 1, 1, 0, "inplace4 per polynomial, nt in/out"));
+    timeit(with(i4p, 0, 0, 1, "inplace4 per polynomial, XCD tile ranges"));
+    timeit(with(i4p, 1, 1, 1, "inplace4 per polynomial, nt + XCD"));
+    for (uint32_t wl : {2u, 3u}) {
+      char nm[96];
+      snprintf(nm, sizeof nm, "inplace2 W=%u per polynomial", 1u << wl);
+      Sched i2{nm, {inplace2(in, s0, out, wl), inplace2(in + N, s0, out + N, wl)}};
+      timeit(i2);
+      snprintf(nm, sizeof nm, "inplace2 W=%u per polynomial, XCD tile ranges", 1u << wl);
+      timeit(with(i2, 0, 0, 1, nm));
+    }
   }
   // 2^20 x 32 (the headline workload): whole batch per pass, or groups of 4 polynomials
   // chained (a group's scratch, 32 MiB, can stay in the Infinity Cache / L2)
@@ -267,6 +290,36 @@ int main() {
       }
     }
   }
+  // the same W = 8 stockham2 with the intermediate tile-major, tile pitch 64 KiB + pad; a
+  // stream's groups share one scratch slot as in the library's ring
+  {
+    Sched sc;
+    sc.name = "2^20x32 stockham2 W=8 groups of 4, two scratch slots";
+    for (int g0 = 0; g0 < 32; g0 += 4) {
+      const uint64_t off = (uint64_t)g0 * n20;
+      sc.seq.push_back(batched(stockham2_20(in + off, s0 + (uint64_t)((g0 / 4) & 1) * 4 * n20, out + off, 3), 4, n20));
+    }
+    timeit(sc);
+    timeit(with(sc, 0, 0, 1, "2^20x32 stockham2 W=8 groups of 4, two scratch slots, XCD"));
+  }
+  for (uint64_t pad : {0ull, 32ull, 160ull}) {
+    for (int grp : {32, 4}) {
+      Sched sc;
+      char* nm = new char[96];
+      snprintf(nm, 96, "2^20x32 stockham2 tile-major pad %llu groups of %d", (unsigned long long)pad, grp);
+      sc.name = nm;
+      for (int g0 = 0; g0 < 32; g0 += grp) {
+        const uint64_t off = (uint64_t)g0 * n20;
+        sc.seq.push_back(blocked2_20(in + off, grp == 32 ? s0 : s0 + (uint64_t)((g0 / grp) & 1) * grp * 128 * (8192 + pad),
+                                     out + off, grp, pad));
+      }
+      timeit(sc);
+      char* nm2 = new char[96];
+      snprintf(nm2, 96, "%s, XCD", nm);
+      timeit(with(sc, 0, 0, 1, nm2));
+    }
+  }
+  if (only20) return 0;
   Sched i4b{"inplace4 two S (no reuse)", {inplace4(in, s0, out), inplace4(in + N, s0 + N, out + N)}};
   timeit(i4b);
   return 0;
