@@ -79,6 +79,8 @@ int pbf_ctx_set_stream(pbf_ctx* ctx, void* stream);
  *   ntt256.l29     0          256-bit NTT passes and the prover's quotient kernel on 8 x 32-bit
  *                             limbs instead of nine 29-bit ones
  *   msm.fx_c       16/20/22   fixed-base MSM window bits (default by size)
+ *   g1ntt.tile_log 6..20      G1 NTT: 2^L twiddle products per launch, each with 15 x 128 B of
+ *                             window table (default 14: 30 MiB)
  *   g1.mul_base    "daa"      G1 fixed-base products by double-and-add instead of the comb
  *   pair.engine    "lane"/"wg" pairing engine (default: lanes from 4096 pairings)
  *   pair.lane_wpe  1 / 2      lane engine built for 1 or 2 waves per SIMD (default by size)
@@ -398,6 +400,59 @@ int pbf_kzg_open_bn254_dev(pbf_ctx* ctx, const uint64_t* d_srs, size_t srs_m, co
                            uint64_t* out_w, void* stream);
 int pbf_kzg_verify_bn254(pbf_ctx* ctx, const uint64_t* g2, size_t count, const uint64_t* commits, const uint64_t* z,
                          const uint64_t* y, const uint64_t* w, const uint64_t* rho, int* ok);
+
+/* ---- KZG in evaluation form: G1 NTT, Lagrange-basis SRS, opening from evaluations -----------
+ * A polynomial of degree < n given by its values on H = <omega> (evals[i] = p(omega^i), as the
+ * NTT entry points leave witness columns, extensions and quotients) is committed and opened as it
+ * stands, with no inverse transform, against the SRS in the Lagrange basis
+ *     lsrs[i] = [L_i(s)]G,   L_i(x) = (x^n - 1) omega^i / (n (x - omega^i)),   i < n.
+ * omega: canonical, of order exactly n; n a power of two, 1 <= n <= 2^28.
+ *
+ * pbf_ntt_g1_bn254*: the NTT over G1 points, natural order in and out:
+ *     inverse = 0:  out[k] = sum_j [omega^(jk)] in[j]
+ *     inverse = 1:  out[j] = [n^-1] sum_k [omega^(-jk)] in[k]
+ *   Points are canonical affine, 8 x u64, (0,0) the identity. The output is the unique canonical
+ *   form, so inverse(forward(x)) == x bit for bit. in == out is allowed. Its main use is the
+ *   Lagrange-basis SRS, computed without the trapdoor:
+ *     lsrs = the inverse G1 NTT of srs[0 .. n).
+ *   The host form checks every point canonical and on the curve (PBF_EINVAL before the
+ *   transform is enqueued). The _dev form does not check, like pbf_ntt_u64_batch_dev: input off
+ *   the curve gives unspecified points, never a fault. Cost: n/2 (log2 n - 1) products of a point
+ *   by a full-width scalar (the inverse: n more), on a 4-bit fixed window. The
+ *   context keeps the table of omega's powers per (omega, n) until pbf_ctx_release_caches, and
+ *   n x 128 B of scratch plus the window table of option g1ntt.tile_log.
+ * Commit from evaluations needs no entry point of its own:
+ *     pbf_kzg_commit_bn254*(lsrs, n, evals, n, pitch, batch, out) = [p_b(s)]G,
+ *   the same points as the commitments of the coefficient forms against srs, and
+ *   pbf_kzg_verify_bn254 verifies them unchanged.
+ * pbf_kzg_open_evals_bn254*: the batched opening of pbf_kzg_open_bn254 from evaluations;
+ *   polynomial b is the n values at evals + b * pitch:
+ *     out_y[b] = p_b(z),   out_w = sum_i q_i lsrs[i],
+ *     q = the values on H of (sum_b weights_b (p_b(x) - out_y[b])) / (x - z),
+ *   the same y and, bit for bit, the same point W as pbf_kzg_open_bn254 returns for the
+ *   coefficient forms. With u_i = 1 / (omega^i - z), c = sum_b weights_b p_b, y_c = sum_b
+ *   weights_b y_b: y_b = -(z^n - 1) n^-1 sum_i p_b[i] omega^i u_i and q_i = (c_i - y_c) u_i: one
+ *   batch inversion, one dot product per polynomial, one pointwise sweep, one fixed-base MSM.
+ *   z inside H is no failing case either: for z = omega^k (found on the device) y_b = p_b[k],
+ *   q_i as above for i != k, and q_k = -omega^-k sum_{i != k} omega^i q_i; the inversion never
+ *   sees the zero denominator. n = 1: y_b = p_b[0], W is the identity and lsrs is not read.
+ * One window table per context: the fixed-base MSM caches the window table of ONE point set. A
+ *   caller who alternates srs and lsrs on one context rebuilds that table at every switch;
+ *   two contexts, one per basis, avoid it.
+ * Streams and results as the KZG entry points above (_dev: d_lsrs, d_evals, d_in, d_out on the
+ *   device, everything else on the host; caller's stream only).
+ * Errors (PBF_EINVAL, before anything is enqueued): those of pbf_kzg_open_bn254* with len read as
+ *   n; n = 0, not a power of two or above 2^28; omega >= r or not of order exactly n; NULL
+ *   pointers; in the host form of the NTT a coordinate >= q or a point off the curve.           */
+int pbf_ntt_g1_bn254(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* in, uint64_t* out, size_t n, int inverse);
+int pbf_ntt_g1_bn254_dev(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* d_in, uint64_t* d_out, size_t n,
+                         int inverse, void* stream);
+int pbf_kzg_open_evals_bn254(pbf_ctx* ctx, const uint64_t* lsrs, size_t n, const uint64_t* omega,
+                             const uint64_t* evals, size_t pitch, size_t batch, const uint64_t* z,
+                             const uint64_t* weights, uint64_t* out_y, uint64_t* out_w);
+int pbf_kzg_open_evals_bn254_dev(pbf_ctx* ctx, const uint64_t* d_lsrs, size_t n, const uint64_t* omega,
+                                 const uint64_t* d_evals, size_t pitch, size_t batch, const uint64_t* z,
+                                 const uint64_t* weights, uint64_t* out_y, uint64_t* out_w, void* stream);
 
 /* Config 5 across G GPUs ("NTT sharded across 8xMI355X"): one process (or thread) per GPU
  * calls pbf_plonk_prove_bn254_sharded_dev with the same inputs (circuit, SRS, challenges,

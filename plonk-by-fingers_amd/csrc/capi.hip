@@ -114,6 +114,7 @@ int pbf_ctx_release_caches(pbf_ctx* ctx) {
   ctx->fixed_base.n = 0;
   ctx->fixed_base.table.release();
   ctx->fixed_base.inf.release();
+  ctx->domain_tw.clear();
   for (const char* name : {"pk.coef", "pk.coset", "pc.lines", "pc.qinf"}) ctx->named.erase(name);
   for (auto it = ctx->named.begin(); it != ctx->named.end();)
     it = it->first.compare(0, 5, "snap.") == 0 ? ctx->named.erase(it) : std::next(it);
@@ -131,7 +132,8 @@ int pbf_ctx_set_option(pbf_ctx* ctx, const char* name, const char* value) {
   static const char* const known[] = {"ntt.passes",  "ntt.group",       "ntt.streams",   "ntt.twmax_log",
                                       "ntt.twsplit", "ntt.no_rg",       "ntt256.maxr",   "ntt256.twlog",
                                       "msm.fx_c",    "g1.mul_base",     "pair.engine",   "pair.lane_wpe",
-                                      "prover.pk",   "prover.timing",   "verifier.vk",   "ntt256.l29"};
+                                      "prover.pk",   "prover.timing",   "verifier.vk",   "ntt256.l29",
+                                      "g1ntt.tile_log"};
   bool ok = false;
   for (const char* k : known) ok = ok || strcmp(k, name) == 0;
   if (!ok) return fail(PBF_EINVAL, std::string("unknown option ") + name);

@@ -376,4 +376,20 @@ struct G1Quad {
   }
 };
 
+// an ABI point (8 x u64) that is not a group element: a coordinate >= q or off the curve.
+// canonical coordinates on y^2 = x^3 + 3; the identity (0, 0) is accepted (G1P::in_curve)
+__device__ inline bool g1_bad(const uint64_t* p) {
+  uint64_t l[8], any = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) any |= (l[k] = p[k]);
+  if (any == 0) return false;
+  const U256 x = u256_from_u64(l), y = u256_from_u64(l + 4);
+  if (Fq::geq_p(x) || Fq::geq_p(y)) return true;
+  const U256 xm = Fq::to_mont(x), ym = Fq::to_mont(y);
+  U256 three = u256_zero();
+  three.w[0] = 3;
+  const U256 rhs = Fq::add(Fq::mul(Fq::mul(xm, xm), xm), Fq::to_mont(three));
+  return !Fq::eq(Fq::mul(ym, ym), rhs);
+}
+
 }  // namespace pbf

@@ -1,0 +1,262 @@
+// NTT over BN254 G1 on gfx950 (include/pbf.h "KZG in evaluation form"): out[k] = sum_j
+// [omega^(jk)] in[j] over points, and the evaluation domain H = <omega> it shares with the
+// opening from evaluations (kzg.hip). Its main use is the Lagrange-basis SRS: the inverse
+// transform of [s^j]G is [L_i(s)]G, with no trapdoor.
+//
+//   load      canonical affine in[i] -> Xyzz (Montgomery) at scratch[bitrev(i)]; the transform
+//             runs in the scratch, so in and out may be one buffer
+//   stages    log2 n radix-2 decimation-in-time launches, one lane per butterfly
+//             (P, Q) -> (P + [w]Q, P - [w]Q), w = omega^(j n / 2h) for position j of a group of
+//             half-width h. The first stage (h = 1) and position 0 of every group have w = 1 and
+//             skip the product. With the table holding omega^i for i < n/2 only, no twiddle is
+//             -1: the butterfly's own subtraction is the negation.
+//   store     Xyzz -> canonical affine (to_affine_plain). The inverse is the forward transform
+//             read back at index (n - i) mod n, times n^-1: one product per point in this pass,
+//             none added to the butterflies.
+//
+// [w]Q is a fixed 4-bit unsigned window: the lane writes 1Q .. 15Q (one dbl2, thirteen add2) to
+// its own 15 x 128 B of a context scratch table, then 64 windows of four doublings and one
+// addition of the table entry its digit names (none for digit 0). The digits come from the
+// scalar's words in memory by shifts, and the entry by address, so no register array is indexed
+// at run time. A launch covers at most 2^g1ntt.tile_log products (2^14: a 30 MiB table); wider
+// stages run as several launches over the same table. Stages with h < 64 map lanes position-
+// major, so that a wave shares one twiddle (uniform digits, uniform skips) whenever the stage
+// has 64 groups or more. Every group operation is add2 / dbl2, the complete forms: a butterfly's
+// operands can be equal, opposite or the identity (tests/test_g1_ntt_gpu.py builds each case).
+#include <algorithm>
+#include <cstring>
+#include <vector>
+#include "../../include/pbf.h"
+#include "prover.hpp"
+
+using namespace pbf;
+
+namespace {
+
+constexpr int GN_T = 64;          // lanes per workgroup: one wave, one product per lane
+constexpr int GN_ENT = 15;        // table entries per product: 1Q .. 15Q
+constexpr int GN_JM_LOG = 6;      // stages with half-width below 2^6 map lanes position-major
+constexpr int GN_TILE_LOG = 14;   // products per launch (option g1ntt.tile_log, 6 .. 20)
+
+__device__ __forceinline__ Xyzz ld_pt(const Xyzz* p) {
+  const uint4* s = (const uint4*)p;
+  uint4 v[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = s[i];
+  Xyzz r;
+  memcpy(&r, v, sizeof(Xyzz));
+  return r;
+}
+__device__ __forceinline__ void st_pt(Xyzz* p, const Xyzz& r) {
+  uint4 v[8];
+  memcpy(v, &r, sizeof(Xyzz));
+  uint4* d = (uint4*)p;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) d[i] = v[i];
+}
+
+// [k]Q for the canonical scalar at k (8 x u32 in memory); tbl: this lane's first table entry,
+// the others `stride` points apart
+__device__ __forceinline__ Xyzz g1_mul_win(const Xyzz& Q, const uint32_t* k, Xyzz* tbl, uint64_t stride) {
+  if (G1::is_identity(Q)) return Q;
+  st_pt(tbl, Q);
+  Xyzz acc = G1::dbl2(Q);
+  st_pt(tbl + stride, acc);
+#pragma unroll 1
+  for (int e = 2; e < GN_ENT; ++e) {
+    acc = G1::add2(acc, Q);
+    st_pt(tbl + e * stride, acc);
+  }
+  acc = G1::identity();
+#pragma unroll 1
+  for (int i = 63; i >= 0; --i) {
+#pragma unroll 1
+    for (int d = 0; d < 4; ++d) acc = G1::dbl2(acc);  // the identity returns at once
+    const uint32_t digit = (k[i >> 3] >> ((i & 7) * 4)) & 15u;
+    if (digit) acc = G1::add2(acc, ld_pt(tbl + (digit - 1) * stride));
+  }
+  return acc;
+}
+
+__global__ void __launch_bounds__(256) k_g1_check(const uint64_t* in, uint64_t n, int* flag) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n && g1_bad(in + 8 * i)) atomicOr(flag, 1);
+}
+
+__global__ void __launch_bounds__(256) k_g1_load(const uint64_t* in, Xyzz* x, uint64_t n, uint32_t log_n) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  uint64_t l[8], any = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) any |= (l[k] = in[8 * i + k]);
+  Xyzz p = G1::identity();
+  if (any) {
+    Affine a;
+    a.x = Fq::to_mont(u256_from_u64(l));
+    a.y = Fq::to_mont(u256_from_u64(l + 4));
+    p = G1::from_affine(a);
+  }
+  const uint64_t r = log_n ? __brevll(i) >> (64 - log_n) : 0;
+  st_pt(x + r, p);
+}
+
+// One stage: butterflies [b0, b0 + count) of the n/2, half-width 2^log_half
+__global__ void __launch_bounds__(GN_T) __attribute__((amdgpu_waves_per_eu(2))) k_g1_stage(Xyzz* x, const uint64_t* tw, Xyzz* tbl, uint64_t stride, uint64_t b0,
+                                                   uint64_t count, uint32_t log_half, uint32_t log_n) {
+  const uint64_t t = (uint64_t)blockIdx.x * GN_T + threadIdx.x;
+  if (t >= count) return;
+  const uint64_t b = b0 + t;
+  const uint32_t log_groups = log_n - 1 - log_half;
+  uint64_t j, g;
+  if (log_half < GN_JM_LOG) {  // position-major: neighbouring lanes share the twiddle
+    j = b >> log_groups;
+    g = b & (((uint64_t)1 << log_groups) - 1);
+  } else {
+    j = b & (((uint64_t)1 << log_half) - 1);
+    g = b >> log_half;
+  }
+  const uint64_t i0 = (g << (log_half + 1)) + j, i1 = i0 + ((uint64_t)1 << log_half);
+  Xyzz Q = ld_pt(x + i1);
+  if (j) Q = g1_mul_win(Q, (const uint32_t*)(tw + 4 * (j << log_groups)), tbl + t, stride);
+  const Xyzz P = ld_pt(x + i0);  // after the product: not live across it
+  st_pt(x + i0, G1::add2(P, Q));
+  Q.Y = Fq::sub(u256_zero(), Q.Y);
+  st_pt(x + i1, G1::add2(P, Q));
+}
+
+// out[i] for i in [i0, i0 + count): x[i], or for the inverse [n^-1] x[(n - i) mod n]
+__global__ void __launch_bounds__(GN_T) __attribute__((amdgpu_waves_per_eu(2))) k_g1_store(const Xyzz* x, uint64_t* out, const uint32_t* ninv, Xyzz* tbl,
+                                                   uint64_t stride, uint64_t i0, uint64_t count, uint64_t n) {
+  const uint64_t t = (uint64_t)blockIdx.x * GN_T + threadIdx.x;
+  if (t >= count) return;
+  const uint64_t i = i0 + t;
+  Xyzz p = ld_pt(x + (ninv ? (n - i) & (n - 1) : i));
+  if (ninv) p = g1_mul_win(p, ninv, tbl + t, stride);
+  U256 ax, ay;
+  G1::to_affine_plain(p, &ax, &ay);
+  u256_to_u64(ax, out + 8 * i);
+  u256_to_u64(ay, out + 8 * i + 4);
+}
+
+uint32_t blocks_of(uint64_t threads, uint32_t per) { return (uint32_t)((threads + per - 1) / per); }
+
+int ntt_args(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* in, const uint64_t* out, size_t n, U256* wm) {
+  if (!ctx || !omega || !in || !out) return fail(PBF_EINVAL, "null argument");
+  return fr_domain_check(omega, n, wm);
+}
+
+// the transform of n device points, enqueued on s; arguments checked by the caller
+int g1_ntt_run(pbf_ctx* ctx, const U256& wm, const uint64_t* d_in, uint64_t* d_out, uint64_t n, int inverse,
+               hipStream_t s) {
+  if (n == 1) {
+    if (d_in != d_out) PBF_HIP(hipMemcpyAsync(d_out, d_in, 64, hipMemcpyDeviceToDevice, s));
+    return 0;
+  }
+  uint32_t log_n = 0;
+  while (((uint64_t)1 << log_n) < n) ++log_n;
+  const long long tl = std::min<long long>(20, std::max<long long>(6, ctx->options.num("g1ntt.tile_log", GN_TILE_LOG)));
+  const uint64_t tile = (uint64_t)1 << tl, nb = n / 2;
+  const uint64_t stride = std::min(tile, inverse ? n : nb);  // the widest launch that multiplies
+  const uint64_t* tw = nullptr;
+  int rc;
+  if ((rc = fr_domain_table(ctx, wm, n, s, &tw))) return rc;
+  DevBuf &bx = ctx->buf("g1ntt.x"), &bt = ctx->buf("g1ntt.tbl");
+  if ((rc = bx.ensure(n * sizeof(Xyzz))) || (rc = bt.ensure(stride * GN_ENT * sizeof(Xyzz)))) return rc;
+  Xyzz *x = (Xyzz*)bx.p, *tbl = (Xyzz*)bt.p;
+  hipLaunchKernelGGL(k_g1_load, dim3(blocks_of(n, 256)), dim3(256), 0, s, d_in, x, n, log_n);
+  for (uint32_t lh = 0; lh < log_n; ++lh) {
+    const uint64_t step = lh ? stride : nb;  // the first stage has no product and no table
+    for (uint64_t b0 = 0; b0 < nb; b0 += step) {
+      const uint64_t cnt = std::min(step, nb - b0);
+      hipLaunchKernelGGL(k_g1_stage, dim3(blocks_of(cnt, GN_T)), dim3(GN_T), 0, s, x, tw, tbl, stride, b0, cnt, lh,
+                         log_n);
+    }
+  }
+  const uint32_t* ninv = inverse ? (const uint32_t*)(tw + 4 * nb) : nullptr;
+  const uint64_t step = inverse ? stride : n;
+  for (uint64_t i0 = 0; i0 < n; i0 += step) {
+    const uint64_t cnt = std::min(step, n - i0);
+    hipLaunchKernelGGL(k_g1_store, dim3(blocks_of(cnt, GN_T)), dim3(GN_T), 0, s, (const Xyzz*)x, d_out, ninv, tbl,
+                       stride, i0, cnt, n);
+  }
+  PBF_HIP(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+
+namespace pbf {
+
+int fr_domain_check(const uint64_t* omega, size_t n, U256* wm) {
+  if (n == 0 || (n & (n - 1))) return fail(PBF_EINVAL, "n must be a power of two");
+  if (n > ((size_t)1 << 28)) return fail(PBF_EINVAL, "n exceeds the 2-adicity of BN254 Fr (2^28)");
+  if (!fr_canonical(omega)) return fail(PBF_EINVAL, "omega not canonical");
+  *wm = hm(omega);
+  if (n == 1 ? !heq1(*wm) : (!heq1(fr_pow(*wm, n)) || heq1(fr_pow(*wm, n / 2))))
+    return fail(PBF_EINVAL, "omega does not have order n");
+  return 0;
+}
+
+int fr_domain_table(pbf_ctx* ctx, const U256& wm, uint64_t n, hipStream_t s, const uint64_t** tw) {
+  std::array<uint64_t, 5> key;
+  hout(key.data(), wm);
+  key[4] = n;
+  auto& slot = ctx->domain_tw[key];
+  if (!slot) {
+    std::unique_ptr<DevBuf> b(new DevBuf());
+    const uint64_t h = n / 2;
+    int rc = b->ensure((h + 1) * 32);
+    if (rc) {
+      ctx->domain_tw.erase(key);
+      return rc;
+    }
+    uint64_t ninv[4];
+    hout(ninv, fr_inv(hm64(n)));
+    hipError_t e = hipMemcpyAsync((uint64_t*)b->p + 4 * h, ninv, 32, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) rc = fr_powers_run((uint64_t*)b->p, h, wm, fr_one_m(), s);
+    if (e == hipSuccess && !rc) e = hipStreamSynchronize(s);  // other streams may use it next
+    if (e != hipSuccess || rc) {
+      ctx->domain_tw.erase(key);
+      return rc ? rc : fail(PBF_EDEVICE, std::string("domain table: ") + hipGetErrorString(e));
+    }
+    slot = std::move(b);
+  }
+  *tw = (const uint64_t*)slot->p;
+  return 0;
+}
+
+}  // namespace pbf
+
+extern "C" int pbf_ntt_g1_bn254_dev(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* d_in, uint64_t* d_out,
+                                    size_t n, int inverse, void* stream) {
+  U256 wm;
+  int rc = ntt_args(ctx, omega, d_in, d_out, n, &wm);
+  if (rc) return rc;
+  PBF_HIP(hipSetDevice(ctx->device));
+  return g1_ntt_run(ctx, wm, d_in, d_out, n, inverse, (hipStream_t)stream);
+}
+
+extern "C" int pbf_ntt_g1_bn254(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* in, uint64_t* out, size_t n,
+                                int inverse) {
+  U256 wm;
+  int rc = ntt_args(ctx, omega, in, out, n, &wm);
+  if (rc) return rc;
+  PBF_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->host_stream();
+  DevBuf &bio = ctx->buf("g1ntt.io"), &bfl = ctx->buf("g1ntt.flag");
+  if ((rc = bio.ensure(n * 64)) || (rc = bfl.ensure(sizeof(int)))) return rc;
+  uint64_t* io = (uint64_t*)bio.p;
+  PBF_HIP(hipMemcpyAsync(io, in, n * 64, hipMemcpyHostToDevice, s));
+  PBF_HIP(hipMemsetAsync(bfl.p, 0, sizeof(int), s));
+  hipLaunchKernelGGL(k_g1_check, dim3(blocks_of(n, 256)), dim3(256), 0, s, (const uint64_t*)io, (uint64_t)n,
+                     (int*)bfl.p);
+  PBF_HIP(hipGetLastError());
+  int bad = 0;
+  PBF_HIP(hipMemcpyAsync(&bad, bfl.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  PBF_HIP(hipStreamSynchronize(s));
+  if (bad) return fail(PBF_EINVAL, "a point is not canonical or not on the curve");
+  if ((rc = g1_ntt_run(ctx, wm, io, io, n, inverse, s))) return rc;
+  PBF_HIP(hipMemcpyAsync(out, io, n * 64, hipMemcpyDeviceToHost, s));
+  PBF_HIP(hipStreamSynchronize(s));
+  return PBF_OK;
+}

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <array>
 #include <cstdlib>
 #include <map>
 #include <memory>
@@ -245,5 +246,8 @@ struct pbf_ctx {
   // circuit and SRS in vk_key (n, srs_m, k1 k2) while q, copies and the SRS equal their
   // snapshots "vk.q" / "vk.copies" / "vk.srs"
   std::vector<uint64_t> vk_key, vk_pts;
+  // domain tables of the G1 NTT and of KZG in evaluation form (g1_ntt.hip fr_domain_table), by
+  // (omega's 4 limbs, n); freed by pbf_ctx_release_caches
+  std::map<std::array<uint64_t, 5>, std::unique_ptr<pbf::DevBuf>> domain_tw;
   pbf::MsmTail msm_tail;  // destroyed before `named`: its stream drains first
 };

@@ -1016,6 +1016,16 @@ int sigma_table_run(uint64_t n, const U256& omega, const U256& k1, const U256& k
   PBF_HIP(hipGetLastError());
   return 0;
 }
+int fr_powers_run(uint64_t* out, uint64_t count, const U256& base, const U256& start, hipStream_t s) {
+  if (!count) return 0;
+  hipLaunchKernelGGL(k_powers29, dim3(blocks_for((count + PV_CHUNK - 1) / PV_CHUNK)), dim3(256), 0, s, out, count,
+                     powers_tab29(base, start));
+  PBF_HIP(hipGetLastError());
+  return 0;
+}
+int fr_inv_batch_run(pbf_ctx* ctx, const uint64_t* den, uint64_t* out, uint64_t count, int* bad, hipStream_t s) {
+  return div_batch(ctx, nullptr, den, out, count, bad, s);
+}
 
 }  // namespace pbf
 

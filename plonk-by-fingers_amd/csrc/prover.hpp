@@ -39,6 +39,27 @@ int fr_lincomb_run(int k, const uint64_t* const* in, const uint64_t* lens, const
 // sigma[col][i] (3 n values); a label out of range sets *bad: k_powers29, k_sigma
 int sigma_table_run(uint64_t n, const U256& omega, const U256& k1, const U256& k2, const uint64_t* d_copies,
                     uint64_t* hpow, uint64_t* sigma, int* bad, hipStream_t s);
+// out[i] = start base^i (i < count), canonical; base and start in Montgomery form: k_powers29
+int fr_powers_run(uint64_t* out, uint64_t count, const U256& base, const U256& start, hipStream_t s);
+// out[i] = the Montgomery form of 1 / den[i] for canonical den (i < count; out may be den): the
+// prover's batch inversion k_div_batch_w, one Fermat inverse per chunk of 64 x 32 elements or more.
+// A zero denominator sets *bad and leaves its chunk unwritten.
+int fr_inv_batch_run(pbf_ctx* ctx, const uint64_t* den, uint64_t* out, uint64_t count, int* bad, hipStream_t s);
+
+// g1_ntt.hip: the evaluation domain H = <omega> of the G1 NTT and of KZG in evaluation form.
+// n a power of two in 1 .. 2^28 and omega canonical of order exactly n, else PBF_EINVAL;
+// *wm = omega in Montgomery form.
+int fr_domain_check(const uint64_t* omega, size_t n, U256* wm);
+// The context's device table of (omega, n): omega^i canonical for i < n/2 (omega^(i + n/2) is
+// the negation), then n^-1 canonical at entry n/2. Built once per (omega, n) on s by
+// fr_powers_run (one stream sync), kept until pbf_ctx_release_caches.
+int fr_domain_table(pbf_ctx* ctx, const U256& wm, uint64_t n, hipStream_t s, const uint64_t** tw);
+// omega^i from that table, canonical (i < n, n >= 2)
+__device__ __forceinline__ U256 fr_domain_at(const uint64_t* tw, uint64_t n, uint64_t i) {
+  const uint64_t h = n >> 1;
+  const U256 w = u256_from_u64(tw + 4 * (i & (h - 1)));
+  return i < h ? w : Fr::sub(u256_zero(), w);
+}
 
 // verify.hip: Plonk::verify's preprocessing, shared by the single and the batched verifier:
 // pre = the commitments of q_m q_l q_r q_o q_c s_sigma_1..3 (canonical affine), from the

@@ -125,6 +125,11 @@ SIGNATURES = [
     ("pbf_kzg_open_bn254_dev", ctypes.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _p64, _p64, _p64, _p64, _vp]),
     ("pbf_kzg_verify_bn254", ctypes.c_int, [_vp, _p64, _sz, _p64, _p64, _p64, _p64, _p64,
                                             ctypes.POINTER(ctypes.c_int)]),
+    ("pbf_ntt_g1_bn254", ctypes.c_int, [_vp, _p64, _p64, _p64, _sz, ctypes.c_int]),
+    ("pbf_ntt_g1_bn254_dev", ctypes.c_int, [_vp, _p64, _vp, _vp, _sz, ctypes.c_int, _vp]),
+    ("pbf_kzg_open_evals_bn254", ctypes.c_int, [_vp, _p64, _sz, _p64, _p64, _sz, _sz, _p64, _p64, _p64, _p64]),
+    ("pbf_kzg_open_evals_bn254_dev", ctypes.c_int, [_vp, _vp, _sz, _p64, _vp, _sz, _sz, _p64, _p64, _p64, _p64,
+                                                    _vp]),
 ]
 
 _lib = None
@@ -575,6 +580,52 @@ class Context:
                                              _ptr(_g1_limbs([e[3] for e in entries])),
                                              _ptr(ints_to_limbs(list(rhos))), ctypes.byref(ok)))
         return ok.value == 1
+
+    # ---- KZG in evaluation form (include/pbf.h "KZG in evaluation form"; g1_ntt.hip, kzg.hip)
+    def ntt_g1(self, omega: int, points, inverse: bool = False) -> list:
+        """pbf_ntt_g1_bn254: out[k] = sum_j [omega^(jk)] points[j] (the inverse: omega^-1 and
+        n^-1); points as (x, y), the identity (0, 0). The points are checked on the curve."""
+        n = len(points)
+        out = np.zeros(8 * max(n, 1), dtype=np.uint64)
+        _check(self.lib.pbf_ntt_g1_bn254(self.h, _ptr(ints_to_limbs([omega])), _ptr(_g1_limbs(points)), _ptr(out),
+                                         n, int(inverse)))
+        return self._points(out)[:n]
+
+    def ntt_g1_dev(self, omega: int, d_in: int, d_out: int, n: int, inverse: bool = False, stream: int = 0) -> None:
+        """The same on n device points (8 x u64 each, unchecked), enqueued on stream; d_in may be
+        d_out."""
+        _check(self.lib.pbf_ntt_g1_bn254_dev(self.h, _ptr(ints_to_limbs([omega])), _vp(d_in), _vp(d_out), n,
+                                             int(inverse), _vp(stream) if stream else None))
+
+    def srs_lagrange(self, srs, n: int, omega: int | None = None) -> list:
+        """The Lagrange-basis SRS [L_i(s)]G, i < n, of srs = [s^j G]: the inverse G1 NTT of its
+        first n points (no trapdoor). omega defaults to the library's root of unity of order n."""
+        if n < 1 or n & (n - 1) or len(srs) < n:
+            raise ValueError("n must be a power of two within the SRS")
+        if omega is None:
+            omega = pow(5, (BN254_R - 1) // n, BN254_R)  # fr_root_of_unity (csrc/fr_host.hpp)
+        return self.ntt_g1(omega, list(srs[:n]), inverse=True)
+
+    def kzg_open_evals(self, lsrs, omega: int, evals, z: int, weights, pitch: int | None = None):
+        """pbf_kzg_open_evals_bn254: kzg_open for polynomials given by their n values on <omega>
+        against the Lagrange-basis SRS: ([p_b(z)], W), the same W as kzg_open's."""
+        a, n, pitch, batch = self._poly_limbs(evals, pitch)
+        ys = np.zeros(4 * max(batch, 1), dtype=np.uint64)
+        w = np.zeros(8, dtype=np.uint64)
+        _check(self.lib.pbf_kzg_open_evals_bn254(self.h, _ptr(_g1_limbs(lsrs[:n])), n, _ptr(ints_to_limbs([omega])),
+                                                 _ptr(a), pitch, batch, _ptr(ints_to_limbs([z])),
+                                                 _ptr(ints_to_limbs(list(weights))), _ptr(ys), _ptr(w)))
+        return limbs_to_ints(ys)[:batch], self._points(w)[0]
+
+    def kzg_open_evals_dev(self, d_lsrs: int, n: int, omega: int, d_evals: int, pitch: int, batch: int, z: int,
+                           weights, stream: int = 0):
+        ys = np.zeros(4 * max(batch, 1), dtype=np.uint64)
+        w = np.zeros(8, dtype=np.uint64)
+        _check(self.lib.pbf_kzg_open_evals_bn254_dev(self.h, _vp(d_lsrs), n, _ptr(ints_to_limbs([omega])),
+                                                     _vp(d_evals), pitch, batch, _ptr(ints_to_limbs([z])),
+                                                     _ptr(ints_to_limbs(list(weights))), _ptr(ys), _ptr(w),
+                                                     _vp(stream) if stream else None))
+        return limbs_to_ints(ys)[:batch], self._points(w)[0]
 
     def plonk_prove_bn254_sharded_dev(self, comm: "Comm", n, d_q, d_copies, d_abc, chal, rnd, d_srs, srs_m,
                                       k1k2=(2, 3), mode=0, stream: int = 0):
