@@ -454,6 +454,65 @@ int pbf_kzg_open_evals_bn254_dev(pbf_ctx* ctx, const uint64_t* d_lsrs, size_t n,
                                  const uint64_t* d_evals, size_t pitch, size_t batch, const uint64_t* z,
                                  const uint64_t* weights, uint64_t* out_y, uint64_t* out_w, void* stream);
 
+/* ---- Every opening at once: the pointwise G1 product and FK20 over the G1 NTT ----------------
+ * All n openings of a polynomial on its domain, W_i for z = omega^i, i < n (the multiproofs of
+ * data-availability sampling and vector-commitment lookups), from two G1 transforms instead of
+ * n calls of pbf_kzg_open_bn254* (Feist-Khovratovich). Elements as above.
+ *
+ * pbf_g1_bn254_mul*: out_i = [scalars_i] points_i, i < n: a different point for every scalar
+ *   (pbf_g1_bn254_mul_base_dev multiplies G only; the MSM sums). Points canonical affine, (0,0)
+ *   the identity; scalars canonical; the output is the unique canonical affine form. out may be
+ *   points. 1 <= n <= 2^32. The host form checks every point canonical and on the curve and every
+ *   scalar < r (PBF_EINVAL before the product is enqueued); the _dev form does not check, like
+ *   pbf_ntt_g1_bn254_dev: input off the curve gives unspecified points, never a fault. The
+ *   window product of the G1 NTT, on its window table (option g1ntt.tile_log).
+ *
+ * With srs[k] = [s^k]G, p(x) = sum_{j<n} p_j x^j (coefficients past len are zero), omega2 of
+ * order exactly 2n and omega = omega2^2:
+ *     W_(omega^i) = sum_{m<n} omega^(im) h_m,   h_m = sum_{k=0}^{n-2-m} p_(m+1+k) srs[k],
+ *   h_(n-1) the identity: W is the forward G1 NTT of size n of h, and h_m = c_(n-1+m) for the
+ *   convolution c = a * b of a_t = srs[n-2-t] (t <= n-2, the identity for n-1 <= t < 2n) with
+ *   b_j = p_j (j < n, 0 above), which has degree <= 2n-3 and does not wrap at size 2n.
+ * pbf_kzg_fk20_setup_bn254*: once per (SRS, n), into the caller's buffer of 2n points,
+ *     xext = the forward G1 NTT of size 2n, root omega2, of a       (canonical affine),
+ *   so a caller may also compute or store it. Needs srs_m >= n - 1 (points 0 .. n-2 are read).
+ *   n a power of two, 1 <= n <= 2^27; with n = 1 xext is two identities. The host form checks
+ *   the points it reads; d_xext must not overlap d_srs.
+ * pbf_kzg_open_all_bn254*: polynomials laid out as pbf_kzg_open_bn254* takes them, 1 <= len <= n;
+ *   weights on the host, as there:
+ *     out_y[b*n + i] = p_b(omega^i)  (batch x n values; out_y may be NULL),
+ *     out_w[i] = bit for bit the out_w of pbf_kzg_open_bn254 for the same polynomials and
+ *                weights at z = omega^i  (n points).
+ *   Per call: c = (2n)^-1 sum_b weights_b p_b formed once on coefficients (the inverse
+ *   transform's factor rides on the weights, so the batch costs one transform set whatever its
+ *   size), bhat = the Fr NTT of size 2n of c, the products [bhat_i] xext_i written where the
+ *   unscaled inverse G1 NTT of size 2n reads them, then the forward one of size n over entries
+ *   n-1 .. 2n-2 of its result: 2n + n log2 n + n/2 (log2 n - 1) window products and
+ *   one affine conversion per output point, none in between. The values y are Fr NTTs of size n.
+ *   xext is trusted as the setup wrote it (not checked). With len = 1 every W is the identity.
+ *   Scratch kept by the context: 2n x 128 B of points plus the window table of option
+ *   g1ntt.tile_log (min(2n, 2^tile_log) x 1920 B: 30 MiB by default), 2n x 32 B for bhat and
+ *   len x 32 B for c; the tables of omega2's and omega's powers stay until pbf_ctx_release_caches.
+ * Streams: the caller's stream only. The _dev forms take d_srs, d_xext, d_polys, d_points,
+ *   d_scalars and every output on the device, and their results stay there, stream-ordered;
+ *   omega2 and the weights are on the host. Outputs must not overlap inputs except where stated.
+ * Errors (PBF_EINVAL, before anything is enqueued): those of pbf_kzg_open_bn254* (NULL pointers,
+ *   len = 0, batch = 0 or > 2^16, pitch < len, a weight >= r); len > n; n = 0, not a power of
+ *   two or above 2^27; omega2 >= r or not of order exactly 2n; a short SRS; for the product n = 0.  */
+int pbf_g1_bn254_mul(pbf_ctx* ctx, const uint64_t* points, const uint64_t* scalars, uint64_t* out, size_t n);
+int pbf_g1_bn254_mul_dev(pbf_ctx* ctx, const uint64_t* d_points, const uint64_t* d_scalars, uint64_t* d_out, size_t n,
+                         void* stream);
+int pbf_kzg_fk20_setup_bn254(pbf_ctx* ctx, const uint64_t* srs, size_t srs_m, const uint64_t* omega2, size_t n,
+                             uint64_t* xext);
+int pbf_kzg_fk20_setup_bn254_dev(pbf_ctx* ctx, const uint64_t* d_srs, size_t srs_m, const uint64_t* omega2, size_t n,
+                                 uint64_t* d_xext, void* stream);
+int pbf_kzg_open_all_bn254(pbf_ctx* ctx, const uint64_t* xext, size_t n, const uint64_t* omega2,
+                           const uint64_t* polys, size_t len, size_t pitch, size_t batch, const uint64_t* weights,
+                           uint64_t* out_y, uint64_t* out_w);
+int pbf_kzg_open_all_bn254_dev(pbf_ctx* ctx, const uint64_t* d_xext, size_t n, const uint64_t* omega2,
+                               const uint64_t* d_polys, size_t len, size_t pitch, size_t batch,
+                               const uint64_t* weights, uint64_t* d_out_y, uint64_t* d_out_w, void* stream);
+
 /* Config 5 across G GPUs ("NTT sharded across 8xMI355X"): one process (or thread) per GPU
  * calls pbf_plonk_prove_bn254_sharded_dev with the same inputs (circuit, SRS, challenges,
  * blinders) and its rank. The library computes nothing collective itself: it calls back

@@ -23,60 +23,23 @@
 // major, so that a wave shares one twiddle (uniform digits, uniform skips) whenever the stage
 // has 64 groups or more. Every group operation is add2 / dbl2, the complete forms: a butterfly's
 // operands can be equal, opposite or the identity (tests/test_g1_ntt_gpu.py builds each case).
+//
+// The window product and the point loads and stores live in g1_win.hpp, shared with the pointwise
+// product (g1_mul.hip). FK20 (kzg.hip) strings the pieces together through prover.hpp without
+// leaving Xyzz: the stages alone are the unscaled transform, and k_g1_slice loads a transform of
+// half the size from the scratch of the one before.
 #include <algorithm>
 #include <cstring>
 #include <vector>
 #include "../../include/pbf.h"
-#include "prover.hpp"
+#include "g1_win.hpp"
 
 using namespace pbf;
 
 namespace {
 
-constexpr int GN_T = 64;          // lanes per workgroup: one wave, one product per lane
-constexpr int GN_ENT = 15;        // table entries per product: 1Q .. 15Q
 constexpr int GN_JM_LOG = 6;      // stages with half-width below 2^6 map lanes position-major
 constexpr int GN_TILE_LOG = 14;   // products per launch (option g1ntt.tile_log, 6 .. 20)
-
-__device__ __forceinline__ Xyzz ld_pt(const Xyzz* p) {
-  const uint4* s = (const uint4*)p;
-  uint4 v[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) v[i] = s[i];
-  Xyzz r;
-  memcpy(&r, v, sizeof(Xyzz));
-  return r;
-}
-__device__ __forceinline__ void st_pt(Xyzz* p, const Xyzz& r) {
-  uint4 v[8];
-  memcpy(v, &r, sizeof(Xyzz));
-  uint4* d = (uint4*)p;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) d[i] = v[i];
-}
-
-// [k]Q for the canonical scalar at k (8 x u32 in memory); tbl: this lane's first table entry,
-// the others `stride` points apart
-__device__ __forceinline__ Xyzz g1_mul_win(const Xyzz& Q, const uint32_t* k, Xyzz* tbl, uint64_t stride) {
-  if (G1::is_identity(Q)) return Q;
-  st_pt(tbl, Q);
-  Xyzz acc = G1::dbl2(Q);
-  st_pt(tbl + stride, acc);
-#pragma unroll 1
-  for (int e = 2; e < GN_ENT; ++e) {
-    acc = G1::add2(acc, Q);
-    st_pt(tbl + e * stride, acc);
-  }
-  acc = G1::identity();
-#pragma unroll 1
-  for (int i = 63; i >= 0; --i) {
-#pragma unroll 1
-    for (int d = 0; d < 4; ++d) acc = G1::dbl2(acc);  // the identity returns at once
-    const uint32_t digit = (k[i >> 3] >> ((i & 7) * 4)) & 15u;
-    if (digit) acc = G1::add2(acc, ld_pt(tbl + (digit - 1) * stride));
-  }
-  return acc;
-}
 
 __global__ void __launch_bounds__(256) k_g1_check(const uint64_t* in, uint64_t n, int* flag) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -138,49 +101,24 @@ __global__ void __launch_bounds__(GN_T) __attribute__((amdgpu_waves_per_eu(2))) 
   u256_to_u64(ay, out + 8 * i + 4);
 }
 
+// FK20 (kzg.hip): the size-n transform's load, from the scratch itself. x holds the 2n points c of
+// the convolution in natural order; h_m = c[n - 1 + m] goes to x[bitrev_n(m)] for m < n - 1, and
+// h_(n-1) = c[2n - 2], always the identity, is written as such. Lane 0 alone reads and writes
+// below n (x[n - 1] -> x[0], then the identity at x[n - 1] = x[bitrev_n(n - 1)]); every other lane
+// reads x[n .. 2n - 2) and writes x[1 .. n - 1), so no lane reads what another writes.
+__global__ void __launch_bounds__(256) k_g1_slice(Xyzz* x, uint64_t n, uint32_t log_n) {
+  const uint64_t m = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (m + 1 >= n) return;
+  const Xyzz p = ld_pt(x + n - 1 + m);
+  st_pt(x + (__brevll(m) >> (64 - log_n)), p);
+  if (m == 0) st_pt(x + n - 1, G1::identity());
+}
+
 uint32_t blocks_of(uint64_t threads, uint32_t per) { return (uint32_t)((threads + per - 1) / per); }
 
 int ntt_args(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* in, const uint64_t* out, size_t n, U256* wm) {
   if (!ctx || !omega || !in || !out) return fail(PBF_EINVAL, "null argument");
   return fr_domain_check(omega, n, wm);
-}
-
-// the transform of n device points, enqueued on s; arguments checked by the caller
-int g1_ntt_run(pbf_ctx* ctx, const U256& wm, const uint64_t* d_in, uint64_t* d_out, uint64_t n, int inverse,
-               hipStream_t s) {
-  if (n == 1) {
-    if (d_in != d_out) PBF_HIP(hipMemcpyAsync(d_out, d_in, 64, hipMemcpyDeviceToDevice, s));
-    return 0;
-  }
-  uint32_t log_n = 0;
-  while (((uint64_t)1 << log_n) < n) ++log_n;
-  const long long tl = std::min<long long>(20, std::max<long long>(6, ctx->options.num("g1ntt.tile_log", GN_TILE_LOG)));
-  const uint64_t tile = (uint64_t)1 << tl, nb = n / 2;
-  const uint64_t stride = std::min(tile, inverse ? n : nb);  // the widest launch that multiplies
-  const uint64_t* tw = nullptr;
-  int rc;
-  if ((rc = fr_domain_table(ctx, wm, n, s, &tw))) return rc;
-  DevBuf &bx = ctx->buf("g1ntt.x"), &bt = ctx->buf("g1ntt.tbl");
-  if ((rc = bx.ensure(n * sizeof(Xyzz))) || (rc = bt.ensure(stride * GN_ENT * sizeof(Xyzz)))) return rc;
-  Xyzz *x = (Xyzz*)bx.p, *tbl = (Xyzz*)bt.p;
-  hipLaunchKernelGGL(k_g1_load, dim3(blocks_of(n, 256)), dim3(256), 0, s, d_in, x, n, log_n);
-  for (uint32_t lh = 0; lh < log_n; ++lh) {
-    const uint64_t step = lh ? stride : nb;  // the first stage has no product and no table
-    for (uint64_t b0 = 0; b0 < nb; b0 += step) {
-      const uint64_t cnt = std::min(step, nb - b0);
-      hipLaunchKernelGGL(k_g1_stage, dim3(blocks_of(cnt, GN_T)), dim3(GN_T), 0, s, x, tw, tbl, stride, b0, cnt, lh,
-                         log_n);
-    }
-  }
-  const uint32_t* ninv = inverse ? (const uint32_t*)(tw + 4 * nb) : nullptr;
-  const uint64_t step = inverse ? stride : n;
-  for (uint64_t i0 = 0; i0 < n; i0 += step) {
-    const uint64_t cnt = std::min(step, n - i0);
-    hipLaunchKernelGGL(k_g1_store, dim3(blocks_of(cnt, GN_T)), dim3(GN_T), 0, s, (const Xyzz*)x, d_out, ninv, tbl,
-                       stride, i0, cnt, n);
-  }
-  PBF_HIP(hipGetLastError());
-  return 0;
 }
 
 }  // namespace
@@ -225,6 +163,89 @@ int fr_domain_table(pbf_ctx* ctx, const U256& wm, uint64_t n, hipStream_t s, con
   return 0;
 }
 
+int g1_work(pbf_ctx* ctx, uint64_t points, uint64_t products, G1Work* w) {
+  const long long tl = std::min<long long>(20, std::max<long long>(6, ctx->options.num("g1ntt.tile_log", GN_TILE_LOG)));
+  w->stride = std::min((uint64_t)1 << tl, products);  // the widest launch that multiplies
+  DevBuf &bx = ctx->buf("g1ntt.x"), &bt = ctx->buf("g1ntt.tbl");
+  int rc;
+  if (points && (rc = bx.ensure(points * sizeof(Xyzz)))) return rc;
+  if ((rc = bt.ensure(w->stride * GN_ENT * sizeof(Xyzz)))) return rc;
+  w->x = (Xyzz*)bx.p;
+  w->tbl = (Xyzz*)bt.p;
+  return 0;
+}
+
+int g1_check_run(pbf_ctx* ctx, const uint64_t* d_pts, uint64_t n, hipStream_t s, int* bad) {
+  DevBuf& bfl = ctx->buf("g1ntt.flag");
+  int rc;
+  if ((rc = bfl.ensure(sizeof(int)))) return rc;
+  PBF_HIP(hipMemsetAsync(bfl.p, 0, sizeof(int), s));
+  hipLaunchKernelGGL(k_g1_check, dim3(blocks_of(n, 256)), dim3(256), 0, s, d_pts, n, (int*)bfl.p);
+  PBF_HIP(hipGetLastError());
+  PBF_HIP(hipMemcpyAsync(bad, bfl.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  PBF_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int g1_ntt_stages(pbf_ctx* ctx, const U256& wm, uint64_t n, const G1Work& w, hipStream_t s) {
+  uint32_t log_n = 0;
+  while (((uint64_t)1 << log_n) < n) ++log_n;
+  const uint64_t nb = n / 2;
+  const uint64_t* tw = nullptr;
+  int rc;
+  if ((rc = fr_domain_table(ctx, wm, n, s, &tw))) return rc;
+  for (uint32_t lh = 0; lh < log_n; ++lh) {
+    const uint64_t step = lh ? w.stride : nb;  // the first stage has no product and no table
+    for (uint64_t b0 = 0; b0 < nb; b0 += step) {
+      const uint64_t cnt = std::min(step, nb - b0);
+      hipLaunchKernelGGL(k_g1_stage, dim3(blocks_of(cnt, GN_T)), dim3(GN_T), 0, s, w.x, tw, w.tbl, w.stride, b0, cnt,
+                         lh, log_n);
+    }
+  }
+  PBF_HIP(hipGetLastError());
+  return 0;
+}
+
+int g1_ntt_slice(const G1Work& w, uint64_t n, hipStream_t s) {
+  uint32_t log_n = 0;
+  while (((uint64_t)1 << log_n) < n) ++log_n;
+  hipLaunchKernelGGL(k_g1_slice, dim3(blocks_of(n, 256)), dim3(256), 0, s, w.x, n, log_n);
+  PBF_HIP(hipGetLastError());
+  return 0;
+}
+
+int g1_ntt_store(const G1Work& w, uint64_t* d_out, uint64_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_g1_store, dim3(blocks_of(n, GN_T)), dim3(GN_T), 0, s, (const Xyzz*)w.x, d_out,
+                     (const uint32_t*)nullptr, w.tbl, w.stride, (uint64_t)0, n, n);
+  PBF_HIP(hipGetLastError());
+  return 0;
+}
+
+int g1_ntt_run(pbf_ctx* ctx, const U256& wm, const uint64_t* d_in, uint64_t* d_out, uint64_t n, int inverse,
+               hipStream_t s) {
+  if (n == 1) {
+    if (d_in != d_out) PBF_HIP(hipMemcpyAsync(d_out, d_in, 64, hipMemcpyDeviceToDevice, s));
+    return 0;
+  }
+  uint32_t log_n = 0;
+  while (((uint64_t)1 << log_n) < n) ++log_n;
+  const uint64_t* tw = nullptr;
+  G1Work w;
+  int rc;
+  if ((rc = fr_domain_table(ctx, wm, n, s, &tw)) || (rc = g1_work(ctx, n, inverse ? n : n / 2, &w))) return rc;
+  hipLaunchKernelGGL(k_g1_load, dim3(blocks_of(n, 256)), dim3(256), 0, s, d_in, w.x, n, log_n);
+  if ((rc = g1_ntt_stages(ctx, wm, n, w, s))) return rc;
+  if (!inverse) return g1_ntt_store(w, d_out, n, s);
+  const uint32_t* ninv = (const uint32_t*)(tw + 4 * (n / 2));
+  for (uint64_t i0 = 0; i0 < n; i0 += w.stride) {
+    const uint64_t cnt = std::min(w.stride, n - i0);
+    hipLaunchKernelGGL(k_g1_store, dim3(blocks_of(cnt, GN_T)), dim3(GN_T), 0, s, (const Xyzz*)w.x, d_out, ninv, w.tbl,
+                       w.stride, i0, cnt, n);
+  }
+  PBF_HIP(hipGetLastError());
+  return 0;
+}
+
 }  // namespace pbf
 
 extern "C" int pbf_ntt_g1_bn254_dev(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* d_in, uint64_t* d_out,
@@ -243,17 +264,12 @@ extern "C" int pbf_ntt_g1_bn254(pbf_ctx* ctx, const uint64_t* omega, const uint6
   if (rc) return rc;
   PBF_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->host_stream();
-  DevBuf &bio = ctx->buf("g1ntt.io"), &bfl = ctx->buf("g1ntt.flag");
-  if ((rc = bio.ensure(n * 64)) || (rc = bfl.ensure(sizeof(int)))) return rc;
+  DevBuf& bio = ctx->buf("g1ntt.io");
+  if ((rc = bio.ensure(n * 64))) return rc;
   uint64_t* io = (uint64_t*)bio.p;
   PBF_HIP(hipMemcpyAsync(io, in, n * 64, hipMemcpyHostToDevice, s));
-  PBF_HIP(hipMemsetAsync(bfl.p, 0, sizeof(int), s));
-  hipLaunchKernelGGL(k_g1_check, dim3(blocks_of(n, 256)), dim3(256), 0, s, (const uint64_t*)io, (uint64_t)n,
-                     (int*)bfl.p);
-  PBF_HIP(hipGetLastError());
   int bad = 0;
-  PBF_HIP(hipMemcpyAsync(&bad, bfl.p, sizeof(int), hipMemcpyDeviceToHost, s));
-  PBF_HIP(hipStreamSynchronize(s));
+  if ((rc = g1_check_run(ctx, io, n, s, &bad))) return rc;
   if (bad) return fail(PBF_EINVAL, "a point is not canonical or not on the curve");
   if ((rc = g1_ntt_run(ctx, wm, io, io, n, inverse, s))) return rc;
   PBF_HIP(hipMemcpyAsync(out, io, n * 64, hipMemcpyDeviceToHost, s));

@@ -14,6 +14,9 @@
 //            Lagrange-basis SRS (g1_ntt.hip): denominators omega^i - z, the prover's batch
 //            inversion, a barycentric dot product per polynomial, the pointwise quotient, one
 //            MSM; z = omega^k is handled on the device and is no failing case either
+//   open all   every opening on H at once by FK20: one Fr NTT of size 2n, 2n pointwise products
+//            against the setup xext, the inverse G1 NTT of size 2n and the forward one of size n,
+//            the three G1 steps in Xyzz throughout (g1_mul.hip, g1_ntt.hip)
 //   verify   e(sum rho_i W_i, [s]G2) e(-sum rho_i (C_i - y_i G + z_i W_i), G2) == 1: one MSM over
 //            count points, one over 2 count + 1, one pairing check
 //
@@ -327,6 +330,46 @@ int open_evals_args(pbf_ctx* ctx, const uint64_t* lsrs, size_t n, const uint64_t
   return fr_domain_check(omega, n, wm);
 }
 
+// ---------------------------------------------------------------- every opening at once (FK20)
+// W_(omega^i) = sum_m omega^(im) h_m with h_m = sum_k p_(m+1+k) srs[k]: h is the upper half of
+// the convolution of a_t = srs[n - 2 - t] with p, taken in a cyclic convolution of size 2n that
+// does not wrap. xext, the size-2n G1 NTT of a, is the setup; a call is one
+// size-2n Fr NTT, 2n pointwise products, the size-2n inverse G1 NTT and the size-n forward one,
+// the last three without leaving Xyzz (g1_mul.hip, g1_ntt.hip).
+constexpr size_t FK20_MAX_N = (size_t)1 << 27;  // 2n stays within the 2-adicity of Fr
+
+// a_t = srs[n - 2 - t] for t <= n - 2 and the identity (0, 0) for n - 1 <= t < 2n
+__global__ void __launch_bounds__(256) k_fk20_a(const uint64_t* srs, uint64_t n, uint64_t* a) {
+  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= 2 * n) return;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) a[8 * t + k] = t + 2 <= n ? srs[8 * (n - 2 - t) + k] : 0;
+}
+
+// n a power of two in 1 .. 2^27 and omega2 canonical of order exactly 2n; *w2m = omega2 (Montgomery)
+int fk20_domain(size_t n, const uint64_t* omega2, U256* w2m) {
+  if (n == 0 || (n & (n - 1)) || n > FK20_MAX_N) return fail(PBF_EINVAL, "n must be a power of two in 1 .. 2^27");
+  return fr_domain_check(omega2, 2 * n, w2m);
+}
+int fk20_setup_args(pbf_ctx* ctx, const uint64_t* srs, size_t srs_m, const uint64_t* omega2, size_t n,
+                    const uint64_t* xext, U256* w2m) {
+  if (!ctx || !srs || !omega2 || !xext) return fail(PBF_EINVAL, "null argument");
+  int rc = fk20_domain(n, omega2, w2m);
+  if (rc) return rc;
+  if (srs_m + 1 < n) return fail(PBF_EINVAL, "SRS too short");
+  return 0;
+}
+int fk20_open_args(pbf_ctx* ctx, const uint64_t* xext, size_t n, const uint64_t* omega2, const uint64_t* polys,
+                   size_t len, size_t pitch, size_t batch, const uint64_t* weights, const uint64_t* out_w, U256* w2m) {
+  if (!omega2 || !weights || !out_w) return fail(PBF_EINVAL, "null argument");
+  int rc = poly_args(ctx, xext, 0, polys, len, pitch, batch, 0);
+  if (rc) return rc;
+  if ((rc = fk20_domain(n, omega2, w2m))) return rc;
+  if (len > n) return fail(PBF_EINVAL, "len exceeds n");
+  if (!fr_canonical(weights, batch)) return fail(PBF_EINVAL, "weights must be canonical");
+  return 0;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- Poly::eval over Fr
@@ -534,4 +577,120 @@ extern "C" int pbf_kzg_open_evals_bn254(pbf_ctx* ctx, const uint64_t* lsrs, size
   if ((rc = upload_polys(ctx, lsrs, n, evals, n, pitch, batch, s))) return rc;
   return pbf_kzg_open_evals_bn254_dev(ctx, (const uint64_t*)ctx->buf("kzg.srs").p, n, omega,
                                       (const uint64_t*)ctx->buf("kzg.polys").p, n, batch, z, weights, out_y, out_w, s);
+}
+
+// ---------------------------------------------------------------- every opening at once (FK20)
+extern "C" int pbf_kzg_fk20_setup_bn254_dev(pbf_ctx* ctx, const uint64_t* d_srs, size_t srs_m, const uint64_t* omega2,
+                                            size_t n, uint64_t* d_xext, void* stream) {
+  U256 w2m;
+  int rc = fk20_setup_args(ctx, d_srs, srs_m, omega2, n, d_xext, &w2m);
+  if (rc) return rc;
+  PBF_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 1) {  // a is two identities, and so is its transform
+    PBF_HIP(hipMemsetAsync(d_xext, 0, 128, s));
+    return PBF_OK;
+  }
+  hipLaunchKernelGGL(k_fk20_a, dim3((uint32_t)((2 * n + 255) / 256)), dim3(256), 0, s, d_srs, (uint64_t)n, d_xext);
+  PBF_HIP(hipGetLastError());
+  return g1_ntt_run(ctx, w2m, d_xext, d_xext, 2 * n, 0, s);
+}
+
+extern "C" int pbf_kzg_fk20_setup_bn254(pbf_ctx* ctx, const uint64_t* srs, size_t srs_m, const uint64_t* omega2,
+                                        size_t n, uint64_t* xext) {
+  U256 w2m;
+  int rc = fk20_setup_args(ctx, srs, srs_m, omega2, n, xext, &w2m);
+  if (rc) return rc;
+  PBF_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->host_stream();
+  const size_t used = n - 1;  // the points the setup reads
+  DevBuf &ds = ctx->buf("kzg.srs"), &dx = ctx->buf("kzg.fk20.xext");
+  if ((rc = ds.ensure(std::max<size_t>(used, 1) * 64)) || (rc = dx.ensure(2 * n * 64))) return rc;
+  if (used) {
+    PBF_HIP(hipMemcpyAsync(ds.p, srs, used * 64, hipMemcpyHostToDevice, s));
+    int bad = 0;
+    if ((rc = g1_check_run(ctx, (const uint64_t*)ds.p, used, s, &bad))) return rc;
+    if (bad) return fail(PBF_EINVAL, "a point is not canonical or not on the curve");
+  }
+  if ((rc = pbf_kzg_fk20_setup_bn254_dev(ctx, (const uint64_t*)ds.p, used, omega2, n, (uint64_t*)dx.p, s))) return rc;
+  PBF_HIP(hipMemcpyAsync(xext, dx.p, 2 * n * 64, hipMemcpyDeviceToHost, s));
+  PBF_HIP(hipStreamSynchronize(s));
+  return PBF_OK;
+}
+
+extern "C" int pbf_kzg_open_all_bn254_dev(pbf_ctx* ctx, const uint64_t* d_xext, size_t n, const uint64_t* omega2,
+                                          const uint64_t* d_polys, size_t len, size_t pitch, size_t batch,
+                                          const uint64_t* weights, uint64_t* d_out_y, uint64_t* d_out_w, void* stream) {
+  U256 w2m;
+  int rc = fk20_open_args(ctx, d_xext, n, omega2, d_polys, len, pitch, batch, weights, d_out_w, &w2m);
+  if (rc) return rc;
+  PBF_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = (hipStream_t)stream;
+  const uint64_t one[4] = {1, 0, 0, 0};
+  const U256 wm = Fr::mul(w2m, w2m);  // omega = omega2^2, of order n
+  uint64_t om[4];
+  hout(om, wm);
+  // y_b = the size-n Fr NTT of p_b, zero-padded from len
+  if (d_out_y && n == 1) {
+    PBF_HIP(hipMemcpy2DAsync(d_out_y, 32, d_polys, pitch * 32, 32, batch, hipMemcpyDeviceToDevice, s));
+  } else if (d_out_y && pitch == len) {
+    if ((rc = pbf_ntt_fr256_coset_batch_dev(ctx, om, one, d_polys, len, d_out_y, n, batch, 0, s))) return rc;
+  } else if (d_out_y) {
+    for (size_t b = 0; b < batch; ++b)
+      if ((rc = pbf_ntt_fr256_coset_batch_dev(ctx, om, one, d_polys + 4 * b * pitch, len, d_out_y + 4 * b * n, n, 1, 0, s)))
+        return rc;
+  }
+  if (len == 1) {  // constants: every quotient is empty, every W the identity
+    PBF_HIP(hipMemsetAsync(d_out_w, 0, n * 64, s));
+    return PBF_OK;
+  }
+  const uint64_t n2 = 2 * (uint64_t)n;
+  DevBuf &bc = ctx->buf("kzg.comb"), &bb = ctx->buf("kzg.fk20.bhat");
+  G1Work w;
+  if ((rc = bc.ensure(len * 32)) || (rc = bb.ensure(n2 * 32)) || (rc = g1_work(ctx, n2, n2, &w))) return rc;
+  uint64_t *comb = (uint64_t*)bc.p, *bhat = (uint64_t*)bb.p;
+  // c = (2n)^-1 sum_b w_b p_b: the inverse transform's factor rides on the weights
+  const U256 inv2n = fr_inv(hm64(n2));
+  for (uint64_t b0 = 0; b0 < batch;) {
+    const uint64_t* in[10];
+    const uint64_t lens[10] = {len, len, len, len, len, len, len, len, len, len};
+    U256 c[10];
+    int k = 0;
+    if (b0) {  // the sum so far
+      in[k] = comb;
+      c[k++] = fr_one_m();
+    }
+    while (k < 10 && b0 < batch) {
+      in[k] = d_polys + 4 * b0 * pitch;
+      c[k++] = Fr::mul(hm(weights + 4 * b0++), inv2n);
+    }
+    if ((rc = fr_lincomb_run(k, in, lens, c, u256_zero(), comb, len, s))) return rc;
+  }
+  if ((rc = pbf_ntt_fr256_coset_batch_dev(ctx, omega2, one, comb, len, bhat, n2, 1, 0, s))) return rc;
+  // chat_i = [bhat_i] xext_i where the inverse transform reads it; c = a * b; h = c[n-1 .. 2n-1); W = NTT_n(h)
+  if ((rc = g1_mul_xyzz_run(w, d_xext, bhat, n2, s)) || (rc = g1_ntt_stages(ctx, w2m, n2, w, s)) ||
+      (rc = g1_ntt_slice(w, n, s)) || (rc = g1_ntt_stages(ctx, wm, n, w, s)))
+    return rc;
+  return g1_ntt_store(w, d_out_w, n, s);
+}
+
+extern "C" int pbf_kzg_open_all_bn254(pbf_ctx* ctx, const uint64_t* xext, size_t n, const uint64_t* omega2,
+                                      const uint64_t* polys, size_t len, size_t pitch, size_t batch,
+                                      const uint64_t* weights, uint64_t* out_y, uint64_t* out_w) {
+  U256 w2m;
+  int rc = fk20_open_args(ctx, xext, n, omega2, polys, len, pitch, batch, weights, out_w, &w2m);
+  if (rc) return rc;
+  PBF_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->host_stream();
+  if ((rc = upload_polys(ctx, xext, 2 * n, polys, len, pitch, batch, s))) return rc;
+  DevBuf &by = ctx->buf("kzg.fk20.y"), &bw = ctx->buf("kzg.fk20.w");
+  if ((out_y && (rc = by.ensure(batch * n * 32))) || (rc = bw.ensure(n * 64))) return rc;
+  if ((rc = pbf_kzg_open_all_bn254_dev(ctx, (const uint64_t*)ctx->buf("kzg.srs").p, n, omega2,
+                                       (const uint64_t*)ctx->buf("kzg.polys").p, len, len, batch, weights,
+                                       out_y ? (uint64_t*)by.p : nullptr, (uint64_t*)bw.p, s)))
+    return rc;
+  if (out_y) PBF_HIP(hipMemcpyAsync(out_y, by.p, batch * n * 32, hipMemcpyDeviceToHost, s));
+  PBF_HIP(hipMemcpyAsync(out_w, bw.p, n * 64, hipMemcpyDeviceToHost, s));
+  PBF_HIP(hipStreamSynchronize(s));
+  return PBF_OK;
 }

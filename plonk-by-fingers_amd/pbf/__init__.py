@@ -130,6 +130,12 @@ SIGNATURES = [
     ("pbf_kzg_open_evals_bn254", ctypes.c_int, [_vp, _p64, _sz, _p64, _p64, _sz, _sz, _p64, _p64, _p64, _p64]),
     ("pbf_kzg_open_evals_bn254_dev", ctypes.c_int, [_vp, _vp, _sz, _p64, _vp, _sz, _sz, _p64, _p64, _p64, _p64,
                                                     _vp]),
+    ("pbf_g1_bn254_mul", ctypes.c_int, [_vp, _p64, _p64, _p64, _sz]),
+    ("pbf_g1_bn254_mul_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, _vp]),
+    ("pbf_kzg_fk20_setup_bn254", ctypes.c_int, [_vp, _p64, _sz, _p64, _sz, _p64]),
+    ("pbf_kzg_fk20_setup_bn254_dev", ctypes.c_int, [_vp, _vp, _sz, _p64, _sz, _vp, _vp]),
+    ("pbf_kzg_open_all_bn254", ctypes.c_int, [_vp, _p64, _sz, _p64, _p64, _sz, _sz, _sz, _p64, _p64, _p64]),
+    ("pbf_kzg_open_all_bn254_dev", ctypes.c_int, [_vp, _vp, _sz, _p64, _vp, _sz, _sz, _sz, _p64, _vp, _vp, _vp]),
 ]
 
 _lib = None
@@ -626,6 +632,58 @@ class Context:
                                                      _ptr(ints_to_limbs(list(weights))), _ptr(ys), _ptr(w),
                                                      _vp(stream) if stream else None))
         return limbs_to_ints(ys)[:batch], self._points(w)[0]
+
+    # ---- every opening at once (include/pbf.h "Every opening at once"; g1_mul.hip, kzg.hip)
+    def g1_mul(self, points, scalars) -> list:
+        """pbf_g1_bn254_mul: [[k_i] P_i]; points as (x, y), the identity (0, 0). Points are
+        checked on the curve and scalars < r."""
+        n = len(scalars)
+        if len(points) != n:
+            raise ValueError("one scalar per point")
+        out = np.zeros(8 * max(n, 1), dtype=np.uint64)
+        _check(self.lib.pbf_g1_bn254_mul(self.h, _ptr(_g1_limbs(points)), _ptr(ints_to_limbs(list(scalars))),
+                                         _ptr(out), n))
+        return self._points(out)[:n]
+
+    def g1_mul_dev(self, d_points: int, d_scalars: int, d_out: int, n: int, stream: int = 0) -> None:
+        """The same on n device points and scalars (unchecked), enqueued on stream; d_out may be
+        d_points."""
+        _check(self.lib.pbf_g1_bn254_mul_dev(self.h, _vp(d_points), _vp(d_scalars), _vp(d_out), n,
+                                             _vp(stream) if stream else None))
+
+    def kzg_fk20_setup(self, srs, n: int, omega2: int) -> list:
+        """pbf_kzg_fk20_setup_bn254: the 2n points xext of (srs, n) for omega2 of order 2n."""
+        out = np.zeros(16 * max(n, 1), dtype=np.uint64)
+        _check(self.lib.pbf_kzg_fk20_setup_bn254(self.h, _ptr(_g1_limbs(srs) if len(srs) else np.zeros(8, np.uint64)),
+                                                 len(srs), _ptr(ints_to_limbs([omega2])), n, _ptr(out)))
+        return self._points(out)[:2 * n]
+
+    def kzg_fk20_setup_dev(self, d_srs: int, srs_m: int, omega2: int, n: int, d_xext: int, stream: int = 0) -> None:
+        _check(self.lib.pbf_kzg_fk20_setup_bn254_dev(self.h, _vp(d_srs), srs_m, _ptr(ints_to_limbs([omega2])), n,
+                                                     _vp(d_xext), _vp(stream) if stream else None))
+
+    def kzg_open_all(self, xext, omega2: int, polys, weights, pitch: int | None = None, with_y: bool = True):
+        """pbf_kzg_open_all_bn254: every opening on <omega2^2> at once, n = len(xext) / 2:
+        ([[p_b(omega^i)]] or None, [W_i]), each W_i the W of kzg_open at z = omega^i."""
+        a, ln, pitch, batch = self._poly_limbs(polys, pitch)
+        n = len(xext) // 2
+        ys = np.zeros(4 * max(batch * n, 1), dtype=np.uint64)
+        w = np.zeros(8 * max(n, 1), dtype=np.uint64)
+        _check(self.lib.pbf_kzg_open_all_bn254(self.h, _ptr(_g1_limbs(xext)), n, _ptr(ints_to_limbs([omega2])),
+                                               _ptr(a), ln, pitch, batch, _ptr(ints_to_limbs(list(weights))),
+                                               _ptr(ys) if with_y else None, _ptr(w)))
+        v = limbs_to_ints(ys)
+        return ([v[b * n:(b + 1) * n] for b in range(batch)] if with_y else None), self._points(w)[:n]
+
+    def kzg_open_all_dev(self, d_xext: int, n: int, omega2: int, d_polys: int, length: int, pitch: int, batch: int,
+                         weights, d_out_y: int, d_out_w: int, stream: int = 0) -> None:
+        """The same on the device: d_out_y (batch x n values, or 0 for none) and d_out_w (n points)
+        are written on stream and stay there."""
+        _check(self.lib.pbf_kzg_open_all_bn254_dev(self.h, _vp(d_xext), n, _ptr(ints_to_limbs([omega2])),
+                                                   _vp(d_polys), length, pitch, batch,
+                                                   _ptr(ints_to_limbs(list(weights))),
+                                                   _vp(d_out_y) if d_out_y else None, _vp(d_out_w),
+                                                   _vp(stream) if stream else None))
 
     def plonk_prove_bn254_sharded_dev(self, comm: "Comm", n, d_q, d_copies, d_abc, chal, rnd, d_srs, srs_m,
                                       k1k2=(2, 3), mode=0, stream: int = 0):
