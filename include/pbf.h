@@ -513,6 +513,85 @@ int pbf_kzg_open_all_bn254_dev(pbf_ctx* ctx, const uint64_t* d_xext, size_t n, c
                                const uint64_t* d_polys, size_t len, size_t pitch, size_t batch,
                                const uint64_t* weights, uint64_t* d_out_y, uint64_t* d_out_w, void* stream);
 
+/* ---- KZG cell proofs: FK20 over cosets, batched cell verification ----------------------------
+ * Data-availability sampling samples cells, not points: cell i < k = n / l is the l values of p
+ * on the coset {omega^(i + k t) : t < l}, every point of which satisfies x^l = c_i = omega^(i l).
+ * A cell has ONE proof, W_i = [q_i(s)]G for p = q_i (x^l - c_i) + I_i with deg I_i < l (I_i
+ * interpolates p on the cell), and many cells are verified in one pairing check.
+ * n and l are powers of two, 1 <= l <= n <= 2^27; omega2 of order exactly 2n, omega = omega2^2;
+ * srs[j] = [s^j]G; p(x) = sum_{j<n} p_j x^j, coefficients past len zero.
+ *     W_i = sum_{m<k} c_i^m h_m,   h_m = sum_{j=0}^{n-1-(m+1)l} p_(j+(m+1)l) srs[j],
+ *   h_(k-1) the identity: W is the forward G1 NTT of size k, root omega^l, of h. With j = r + l u,
+ *   r < l: h_m = sum_{r<l} (a_r * b_r)_(k-1+m) for the l convolutions of
+ *     a_r[t] = srs[r + l (k-2-t)]  (t <= k-2, the identity for k-1 <= t < 2k)  with
+ *     b_r[u] = p_(r + l u)         (u < k, 0 above),
+ *   none of which wraps at size 2k.
+ * pbf_kzg_cells_setup_bn254*: once per (SRS, n, l), into the caller's buffer of 2n points,
+ *     xext[r*2k + i] = G1-NTT_{2k, omega2^l}(a_r)[i],  r < l, i < 2k   (canonical affine, slab-major),
+ *   so a caller may also compute or store it. Needs srs_m >= n - l (points 0 .. n-l-1 are read).
+ *   With l = 1 the output equals that of pbf_kzg_fk20_setup_bn254* bit for bit; with l = n every
+ *   point is the identity. The l transforms run one after another on the G1 NTT. The host form
+ *   checks the points it reads; d_xext must not overlap d_srs.
+ * pbf_kzg_open_cells_bn254*: polynomials, pitch, batch and the host weights exactly as
+ *   pbf_kzg_open_all_bn254* takes them, 1 <= len <= n:
+ *     out_w[i] = W_i of c = sum_b weights_b p_b, i < k   (k points),
+ *     out_y[(b*k + i)*l + t] = p_b(omega^(i + k t))      (batch x n values, cell-major: the l
+ *                values of a cell are consecutive, in the order the verifier takes them;
+ *                out_y may be NULL).
+ *   Per call: c = (2k)^-1 sum_b weights_b p_b (the inverse transform's factor rides on the
+ *   weights), bhat_r = the Fr NTT of size 2k, root omega2^l, of b_r, all l in one batch; the 2n
+ *   products [bhat_(r,i)] xext_(r,i) as one vector; chat_i = their sum over r < l, written where
+ *   the unscaled inverse G1 NTT of size 2k reads it; then the forward one of size k over entries
+ *   k-1 .. 2k-2 of its result: 2n + k log2 k + k/2 (log2 k - 1) window products, 2k (l - 1)
+ *   additions and one affine conversion per output point, nothing leaving Xyzz in between. The
+ *   values y are the batched Fr NTT of size n followed by a transposing store. xext is trusted as
+ *   the setup wrote it (not checked). With len <= l every W is the identity. With l = 1 out_w and
+ *   out_y equal those of pbf_kzg_open_all_bn254* bit for bit.
+ *   Scratch kept by the context: (2n + 2k) x 128 B of points plus the window table of option
+ *   g1ntt.tile_log, 2n x 32 B for bhat, n x 32 B for the b_r, len x 32 B for c and, with out_y and
+ *   1 < l < n, batch x n x 32 B; the power tables of omega2^l, omega^l and omega stay until
+ *   pbf_ctx_release_caches.
+ * pbf_kzg_verify_cells_bn254: host pointers, like pbf_kzg_verify_bn254. g2 = [G2, [s^l]G2]: the
+ *   caller brings the l-th power of s on the twist, not [s]G2 (a trusted setup publishes it; tests
+ *   make it from a trapdoor with pbf_g2_bn254_mul). srs = the first l G1 points, srs_m >= l; omega
+ *   of order exactly n. Entry j < count is (commits_j, cell_idx_j, ys[j*l .. (j+1)*l), w_j):
+ *   cell_idx is uint64_t, each < k; ys is count x l values in the order of out_y. With
+ *     I_(j,t) = omega^(-idx_j t) INTT_{l, omega^k}(ys_j)[t]   (the interpolant's coefficients),
+ *   *ok = 1 exactly when
+ *     e(sum_j rho_j W_j, [s^l]G2) e(-(sum_j rho_j C_j - [sum_j rho_j I_j](s) G
+ *                                      + sum_j rho_j c_(idx_j) W_j), G2) == 1:
+ *   one batched Fr INTT of size l over the count cells, one sweep, one MSM over count points, one
+ *   over 2 count + l points ((C_j, rho_j), (W_j, rho_j c_(idx_j)), (srs[t], -sum_j rho_j I_(j,t))),
+ *   one pairing check. Repeated cells and repeated commitments are allowed. count in 1 .. 2^20 and
+ *   count * l <= 2^22. The context keeps the power table of (omega, n) (n/2 x 32 B).
+ *   Randomness: the library reads none (the contract of pbf_kzg_verify_bn254). Soundness rests on
+ *   the caller choosing the weights rho, nonzero and canonical, unpredictably and AFTER seeing the
+ *   cells and proofs; with predictable or equal weights the errors of two bad entries can cancel
+ *   (the same cell twice with one value raised by d in one copy and lowered by d in the other,
+ *   under rho = 1, 1) and the batch passes. A point (of commits, w or srs) that is not canonical
+ *   or not on the curve gives *ok = 0 outright ((0,0) is accepted); there is no per-entry
+ *   localisation.
+ * Streams: as the entry points above; the _dev forms take d_srs, d_xext, d_polys and every output
+ *   on the device, omega2 and the weights on the host.
+ * Errors (PBF_EINVAL, before anything is enqueued; never an abort): those of
+ *   pbf_kzg_open_all_bn254* and pbf_kzg_verify_bn254; l = 0, not a power of two or above n; a short
+ *   SRS (srs_m < n - l for the setup, srs_m < l for the verifier); cell_idx >= k; count * l > 2^22;
+ *   omega not of order exactly n (omega2: 2n); a value of ys >= r.                               */
+int pbf_kzg_cells_setup_bn254(pbf_ctx* ctx, const uint64_t* srs, size_t srs_m, const uint64_t* omega2, size_t n,
+                              size_t l, uint64_t* xext);
+int pbf_kzg_cells_setup_bn254_dev(pbf_ctx* ctx, const uint64_t* d_srs, size_t srs_m, const uint64_t* omega2, size_t n,
+                                  size_t l, uint64_t* d_xext, void* stream);
+int pbf_kzg_open_cells_bn254(pbf_ctx* ctx, const uint64_t* xext, size_t n, size_t l, const uint64_t* omega2,
+                             const uint64_t* polys, size_t len, size_t pitch, size_t batch, const uint64_t* weights,
+                             uint64_t* out_y, uint64_t* out_w);
+int pbf_kzg_open_cells_bn254_dev(pbf_ctx* ctx, const uint64_t* d_xext, size_t n, size_t l, const uint64_t* omega2,
+                                 const uint64_t* d_polys, size_t len, size_t pitch, size_t batch,
+                                 const uint64_t* weights, uint64_t* d_out_y, uint64_t* d_out_w, void* stream);
+int pbf_kzg_verify_cells_bn254(pbf_ctx* ctx, const uint64_t* g2, const uint64_t* srs, size_t srs_m,
+                               const uint64_t* omega, size_t n, size_t l, size_t count, const uint64_t* commits,
+                               const uint64_t* cell_idx, const uint64_t* ys, const uint64_t* w, const uint64_t* rho,
+                               int* ok);
+
 /* Config 5 across G GPUs ("NTT sharded across 8xMI355X"): one process (or thread) per GPU
  * calls pbf_plonk_prove_bn254_sharded_dev with the same inputs (circuit, SRS, challenges,
  * blinders) and its rank. The library computes nothing collective itself: it calls back

@@ -136,6 +136,13 @@ SIGNATURES = [
     ("pbf_kzg_fk20_setup_bn254_dev", ctypes.c_int, [_vp, _vp, _sz, _p64, _sz, _vp, _vp]),
     ("pbf_kzg_open_all_bn254", ctypes.c_int, [_vp, _p64, _sz, _p64, _p64, _sz, _sz, _sz, _p64, _p64, _p64]),
     ("pbf_kzg_open_all_bn254_dev", ctypes.c_int, [_vp, _vp, _sz, _p64, _vp, _sz, _sz, _sz, _p64, _vp, _vp, _vp]),
+    ("pbf_kzg_cells_setup_bn254", ctypes.c_int, [_vp, _p64, _sz, _p64, _sz, _sz, _p64]),
+    ("pbf_kzg_cells_setup_bn254_dev", ctypes.c_int, [_vp, _vp, _sz, _p64, _sz, _sz, _vp, _vp]),
+    ("pbf_kzg_open_cells_bn254", ctypes.c_int, [_vp, _p64, _sz, _sz, _p64, _p64, _sz, _sz, _sz, _p64, _p64, _p64]),
+    ("pbf_kzg_open_cells_bn254_dev", ctypes.c_int, [_vp, _vp, _sz, _sz, _p64, _vp, _sz, _sz, _sz, _p64, _vp, _vp,
+                                                    _vp]),
+    ("pbf_kzg_verify_cells_bn254", ctypes.c_int, [_vp, _p64, _p64, _sz, _p64, _sz, _sz, _sz, _p64, _p64, _p64, _p64,
+                                                  _p64, ctypes.POINTER(ctypes.c_int)]),
 ]
 
 _lib = None
@@ -684,6 +691,65 @@ class Context:
                                                    _ptr(ints_to_limbs(list(weights))),
                                                    _vp(d_out_y) if d_out_y else None, _vp(d_out_w),
                                                    _vp(stream) if stream else None))
+
+    # ---- cell proofs (include/pbf.h "KZG cell proofs"; kzg.hip)
+    def kzg_cells_setup(self, srs, n: int, l: int, omega2: int) -> list:
+        """pbf_kzg_cells_setup_bn254: the 2n points xext of (srs, n, l), slab-major, for omega2 of
+        order 2n."""
+        out = np.zeros(16 * max(n, 1), dtype=np.uint64)
+        _check(self.lib.pbf_kzg_cells_setup_bn254(self.h, _ptr(_g1_limbs(srs) if len(srs) else np.zeros(8, np.uint64)),
+                                                  len(srs), _ptr(ints_to_limbs([omega2])), n, l, _ptr(out)))
+        return self._points(out)[:2 * n]
+
+    def kzg_cells_setup_dev(self, d_srs: int, srs_m: int, omega2: int, n: int, l: int, d_xext: int,
+                            stream: int = 0) -> None:
+        _check(self.lib.pbf_kzg_cells_setup_bn254_dev(self.h, _vp(d_srs), srs_m, _ptr(ints_to_limbs([omega2])), n, l,
+                                                      _vp(d_xext), _vp(stream) if stream else None))
+
+    def kzg_open_cells(self, xext, l: int, omega2: int, polys, weights, pitch: int | None = None,
+                       with_y: bool = True):
+        """pbf_kzg_open_cells_bn254: one proof per cell of l points, n = len(xext) / 2, k = n / l:
+        (ys or None, [W_i]) with ys[b][i] the l values p_b(omega^(i + k t)), t < l, of cell i."""
+        a, ln, pitch, batch = self._poly_limbs(polys, pitch)
+        n = len(xext) // 2
+        k = n // l if l else 0
+        ys = np.zeros(4 * max(batch * n, 1), dtype=np.uint64)
+        w = np.zeros(8 * max(k, 1), dtype=np.uint64)
+        _check(self.lib.pbf_kzg_open_cells_bn254(self.h, _ptr(_g1_limbs(xext)), n, l, _ptr(ints_to_limbs([omega2])),
+                                                 _ptr(a), ln, pitch, batch, _ptr(ints_to_limbs(list(weights))),
+                                                 _ptr(ys) if with_y else None, _ptr(w)))
+        v = limbs_to_ints(ys)
+        cells = [[v[(b * k + i) * l:(b * k + i + 1) * l] for i in range(k)] for b in range(batch)]
+        return (cells if with_y else None), self._points(w)[:k]
+
+    def kzg_open_cells_dev(self, d_xext: int, n: int, l: int, omega2: int, d_polys: int, length: int, pitch: int,
+                           batch: int, weights, d_out_y: int, d_out_w: int, stream: int = 0) -> None:
+        """The same on the device: d_out_y (batch x n values, cell-major, or 0 for none) and d_out_w
+        (n / l points) are written on stream and stay there."""
+        _check(self.lib.pbf_kzg_open_cells_bn254_dev(self.h, _vp(d_xext), n, l, _ptr(ints_to_limbs([omega2])),
+                                                     _vp(d_polys), length, pitch, batch,
+                                                     _ptr(ints_to_limbs(list(weights))),
+                                                     _vp(d_out_y) if d_out_y else None, _vp(d_out_w),
+                                                     _vp(stream) if stream else None))
+
+    def kzg_verify_cells(self, g2s, srs, omega: int, n: int, l: int, entries, rhos) -> bool:
+        """pbf_kzg_verify_cells_bn254: g2s = [G2, [s^l]G2]; srs the first l points (or more);
+        entries a list of (C, idx, ys, W) with ys the l values of cell idx; rhos the batching
+        weights: nonzero, < r, chosen unpredictably after seeing the cells (soundness rests on
+        that; include/pbf.h). One pairing check whatever the count."""
+        if len(entries) != len(rhos):
+            raise ValueError("one rho per entry")
+        if any(len(e[2]) != l for e in entries):
+            raise ValueError("l values per cell")
+        ok = ctypes.c_int(-1)
+        _check(self.lib.pbf_kzg_verify_cells_bn254(self.h, _ptr(_g2_limbs(g2s)), _ptr(_g1_limbs(srs)), len(srs),
+                                                   _ptr(ints_to_limbs([omega])), n, l, len(entries),
+                                                   _ptr(_g1_limbs([e[0] for e in entries])),
+                                                   _ptr(_as_u64([e[1] for e in entries])),
+                                                   _ptr(ints_to_limbs([v for e in entries for v in e[2]])),
+                                                   _ptr(_g1_limbs([e[3] for e in entries])),
+                                                   _ptr(ints_to_limbs(list(rhos))), ctypes.byref(ok)))
+        return ok.value == 1
 
     def plonk_prove_bn254_sharded_dev(self, comm: "Comm", n, d_q, d_copies, d_abc, chal, rnd, d_srs, srs_m,
                                       k1k2=(2, 3), mode=0, stream: int = 0):
