@@ -222,6 +222,41 @@ __device__ __forceinline__ uint64_t gl_cs_factor(const GlPassArgs& a, uint64_t i
 
 constexpr int GL_STORES = 16;  // global stores per thread per tile (NSUB_C * C)
 
+// SP 2 exchanges the tile through LDS in two rounds of 32-bit halves (gl_tile), so its LDS
+// block is half of GlShape::LDS * 8 B and three workgroups fit a CU
+__host__ __device__ constexpr bool gl_split(int sp) { return sp == 2; }
+typedef uint32_t gl_u32x2 __attribute__((ext_vector_type(2)));
+// The 16 incoming words of one round, o[i] = the word at p + i * STRIDE / 4, one ds_read_b32 each
+// and waited for. Written out because the compiler pairs such reads into ds_read2st64_b32, whose
+// two results share a register pair: each word then needs a move into its half of its element's
+// own pair (two moves per element and exchange, and 76 B of scratch per lane at 80 VGPRs).
+#define GL_RD(i, off) "ds_read_b32 %" #i ", %16 offset:" #off "\n\t"
+template <int STRIDE>
+__device__ __forceinline__ void gl_lds_read16(const uint32_t* p, uint32_t* o) {
+  static_assert(STRIDE == 512 || STRIDE == 2080, "the strides written out below: Z (C*W words), Y (YP words)");
+  const uint32_t a = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t*)p;
+#define GL_RD_OUT                                                                                                   \
+  "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3]), "=&v"(o[4]), "=&v"(o[5]), "=&v"(o[6]), "=&v"(o[7]), "=&v"(o[8]), \
+      "=&v"(o[9]), "=&v"(o[10]), "=&v"(o[11]), "=&v"(o[12]), "=&v"(o[13]), "=&v"(o[14]), "=&v"(o[15])
+  if constexpr (STRIDE == 512) {
+    asm volatile(GL_RD(0, 0) GL_RD(1, 512) GL_RD(2, 1024) GL_RD(3, 1536) GL_RD(4, 2048) GL_RD(5, 2560) GL_RD(6, 3072)
+                     GL_RD(7, 3584) GL_RD(8, 4096) GL_RD(9, 4608) GL_RD(10, 5120) GL_RD(11, 5632) GL_RD(12, 6144)
+                         GL_RD(13, 6656) GL_RD(14, 7168) GL_RD(15, 7680) "s_waitcnt lgkmcnt(0)"
+                 : GL_RD_OUT
+                 : "v"(a)
+                 : "memory");
+  } else {
+    asm volatile(GL_RD(0, 0) GL_RD(1, 2080) GL_RD(2, 4160) GL_RD(3, 6240) GL_RD(4, 8320) GL_RD(5, 10400) GL_RD(6, 12480)
+                     GL_RD(7, 14560) GL_RD(8, 16640) GL_RD(9, 18720) GL_RD(10, 20800) GL_RD(11, 22880) GL_RD(12, 24960)
+                         GL_RD(13, 27040) GL_RD(14, 29120) GL_RD(15, 31200) "s_waitcnt lgkmcnt(0)"
+                 : GL_RD_OUT
+                 : "v"(a)
+                 : "memory");
+  }
+#undef GL_RD_OUT
+}
+#undef GL_RD
+
 // The tile-major intermediate of SP 2: elements from one 8192-element block to the next. A pad
 // that takes the 128 blocks a first-pass tile writes off the 64-KiB stride measured no faster
 // (DESIGN.md §3.1 round 9), so the blocks are dense; a multiple of 2 keeps the 16-B loads aligned.
@@ -242,7 +277,9 @@ typedef uint64_t gl_u64x2 __attribute__((ext_vector_type(2)));
 // tile-major (GlPassArgs blk_pitch): the first pass's stage C takes 8 digits x 8 columns per
 // wave, so that each of its wave stores (and post_tw loads) is the 512 contiguous bytes of one
 // block; the second pass reads its tile as 64 contiguous KiB, 16 B per lane and load, and its
-// log_ns is the constant LOGR (the index arithmetic of its stores folds to constants).
+// log_ns is the constant LOGR (the index arithmetic of its stores folds to constants). Both
+// exchange the tile through LDS in 32-bit halves, low words first (gl_split below: half the LDS,
+// three workgroups per CU).
 template <int LOGR, int E64, bool FIRST, int TILE, int RG = 0, int CS = 0, int SP = 0>
 __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint32_t tile, uint32_t tiles, int t) {
   using Sh = GlShape<LOGR, TILE>;
@@ -261,6 +298,11 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
   const uint64_t* in = a.in + (uint64_t)poly * a.in_pitch;
   const uint64_t stride = a.n >> LOGR;  // input rows (r) are n/R long
   constexpr bool BLK_IN = SP == 2 && !FIRST, BLK_OUT = SP == 2 && FIRST;
+  // SP 2: both exchanges pass the low words of the tile through LDS first and the high words
+  // second, in the same element indices (Z, yidx) on an array of 32-bit words half the size
+  constexpr bool SPLIT = gl_split(SP);
+  uint32_t* lds32 = (uint32_t*)lds;
+  (void)lds32;
 
   // ---------------- stage A: load, pass twiddle, 4-point DFTs over s1
   uint64_t v[16];
@@ -351,7 +393,50 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
   }
 #pragma unroll
   for (int u = 0; u < 4; ++u) dft_reg<G, 2, sub_root_exp(E64, 2)>(v + u * 4, nullptr, f);
-  if constexpr (BLK_IN) {
+  if constexpr (SPLIT) {
+    // Z in two rounds, low words (hw = 0) then high words: write, barrier, read in stage B's
+    // mapping (below), and a barrier before the high words overwrite the low ones. The outgoing
+    // words of a round are dead before its incoming words arrive.
+    const int q1r = (t >> 6) / Sh::WPQ, rwr = ((t >> 6) % Sh::WPQ) * 64 + (t & 63);
+    uint32_t zl[16];
+#pragma unroll
+    for (int hw = 0; hw < 2; ++hw) {
+      if (hw) __syncthreads();
+      if constexpr (BLK_IN) {
+        // rw = r2*W + w = 2 (t & 63) + b: the two columns of a pair are neighbours in Z
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int s2 = 8 * h + (t >> 6);
+#pragma unroll
+          for (int q1 = 0; q1 < 4; ++q1) {
+            gl_u32x2 e;
+            e.x = (uint32_t)(v[(2 * h) * 4 + bitrev_c(q1, 2)] >> (32 * hw));
+            e.y = (uint32_t)(v[(2 * h + 1) * 4 + bitrev_c(q1, 2)] >> (32 * hw));
+            *(gl_u32x2*)(lds32 + (q1 * 16 + s2) * (C * W) + 2 * (t & 63)) = e;
+          }
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int idx = t + NT * u;  // = s2*(C*W) + (r2*W + w)
+          const int s2 = idx / (C * W), rw = idx % (C * W);
+#pragma unroll
+          for (int q1 = 0; q1 < 4; ++q1)
+            lds32[(q1 * 16 + s2) * (C * W) + rw] = (uint32_t)(v[u * 4 + bitrev_c(q1, 2)] >> (32 * hw));
+        }
+      }
+      __syncthreads();
+      static_assert(C * W * 4 == 512, "Z stride of gl_lds_read16");
+      if (hw == 0) {
+        gl_lds_read16<512>(lds32 + q1r * 16 * (C * W) + rwr, zl);
+      } else {
+        uint32_t zh[16];
+        gl_lds_read16<512>(lds32 + q1r * 16 * (C * W) + rwr, zh);
+#pragma unroll
+        for (int s2 = 0; s2 < 16; ++s2) v[s2] = ((uint64_t)zh[s2] << 32) | zl[s2];
+      }
+    }
+  } else if constexpr (BLK_IN) {
     // rw = r2*W + w = 2 (t & 63) + b: the two columns of a pair are neighbours in Z
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -373,15 +458,30 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
       for (int q1 = 0; q1 < 4; ++q1) lds[(q1 * 16 + s2) * (C * W) + rw] = v[u * 4 + bitrev_c(q1, 2)];
     }
   }
-  __syncthreads();
+  if constexpr (!SPLIT) __syncthreads();
 
   // ---------------- stage B: one q1 per wave; shift twiddles; 16-point DFT over s2
+  // SPLIT: the thread id of everything after stage B's arithmetic, opaque to the compiler there,
+  // so that no address of the Y exchange or the stores is computed early and held across stage B
+  int tc = t;
+  // SPLIT: the 32-bit half hw of stage B's outputs q2 to Y (r2, k1 = q1 + 4 q2, w). W = 8 and
+  // ysw(k1) = q2 & 7: 8 XOR variants of one base, q2 and q2 + 8 an immediate apart
+  auto y_write_half = [&](int hw) {
+    const int wv = tc >> 6, q1 = wv / Sh::WPQ, rw = (wv % Sh::WPQ) * 64 + (tc & 63);
+    const int r2 = rw / W, w = rw % W;
+    static_assert(!SPLIT || (W == 8 && Sh::yidx(3, 2 + 4 * 13, 6) == 3 * YP + 2 * W + (6 ^ (13 & 7)) + 4 * W * 13), "Y address form");
+#pragma unroll
+    for (int q2 = 0; q2 < 16; ++q2)
+      lds32[(r2 * YP + q1 * W + (w ^ (q2 & 7))) + 4 * W * q2] = (uint32_t)(v[bitrev_c(q2, 4)] >> (32 * hw));
+  };
   {
     const int wave = t >> 6;
     const int q1 = wave / Sh::WPQ;
     const int rw = (wave % Sh::WPQ) * 64 + (t & 63);  // r2*W + w
+    if constexpr (!SPLIT) {
 #pragma unroll
-    for (int s2 = 0; s2 < 16; ++s2) v[s2] = lds[(q1 * 16 + s2) * (C * W) + rw];
+      for (int s2 = 0; s2 < 16; ++s2) v[s2] = lds[(q1 * 16 + s2) * (C * W) + rw];
+    }
     if constexpr (RG == 3) {
       uint64_t p = t3[0];
       const uint64_t d = t3[1];
@@ -402,12 +502,20 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
       }
       dft_reg_tail<G, 4, sub_root_exp(E64, 4), GL_B_LEVELS>(v, f);
     }
-    __syncthreads();
-    const int r2 = rw / W, w = rw % W;
+    if constexpr (SPLIT) {
+      asm volatile("" : "+v"(tc));
+      __builtin_assume(tc >= 0 && tc < NT);
+    }
+    __syncthreads();  // every thread has read Z (SPLIT: its high words)
+    if constexpr (SPLIT) {
+      y_write_half(0);
+    } else {
+      const int r2 = rw / W, w = rw % W;
 #pragma unroll
-    for (int q2 = 0; q2 < 16; ++q2) {
-      const int k1 = q1 + 4 * q2;
-      lds[Sh::yidx(r2, k1, w)] = v[bitrev_c(q2, 4)];
+      for (int q2 = 0; q2 < 16; ++q2) {
+        const int k1 = q1 + 4 * q2;
+        lds[Sh::yidx(r2, k1, w)] = v[bitrev_c(q2, 4)];
+      }
     }
   }
   __syncthreads();
@@ -421,11 +529,14 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
   auto c_map = [&](int u, int* k1, int* w) {
     const int idx = t + NT * u;
     if constexpr (BLK_OUT) {
-      *k1 = 8 * (t >> 6) + (t & 7);
-      *w = (t >> 3) & 7;
+      *k1 = 8 * (tc >> 6) + (tc & 7);
+      *w = (tc >> 3) & 7;
     } else if constexpr (FIRST) {
       *k1 = idx & 63;
       *w = idx >> 6;
+    } else if constexpr (SPLIT) {
+      *k1 = tc / W;  // NSUB_C = 1
+      *w = tc % W;
     } else {
       *k1 = idx / W;
       *w = idx % W;
@@ -436,8 +547,22 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
   for (int u = 0; u < Sh::NSUB_C; ++u) {
     int k1, w;
     c_map(u, &k1, &w);
+    if constexpr (SPLIT) {
+      // Y in two rounds like Z: the low words are read, then the high words take their place
+      static_assert(Sh::NSUB_C == 1, "split exchange: one sub-DFT per thread");
+      static_assert(C == 16 && YP * 4 == 2080, "Y stride of gl_lds_read16");
+      uint32_t yl[C], yh[C];
+      gl_lds_read16<2080>(lds32 + Sh::yidx(0, k1, w), yl);
+      __syncthreads();
+      y_write_half(1);
+      __syncthreads();
+      gl_lds_read16<2080>(lds32 + Sh::yidx(0, k1, w), yh);
 #pragma unroll
-    for (int r2 = 0; r2 < C; ++r2) x[u * C + r2] = lds[Sh::yidx(r2, k1, w)];
+      for (int r2 = 0; r2 < C; ++r2) x[r2] = ((uint64_t)yh[r2] << 32) | yl[r2];
+    } else {
+#pragma unroll
+      for (int r2 = 0; r2 < C; ++r2) x[u * C + r2] = lds[Sh::yidx(r2, k1, w)];
+    }
   }
   if constexpr (RG == 3) {
     // w_64^(r2 g), g = k1 >> 2 = wave + 4 u (4-wave tiles, W = 16): wave-uniform shifts
@@ -493,8 +618,8 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
     // element and post_tw entry (block wave + 8 k2, [j0 + w][k1 & 7]): a wave-uniform base plus
     // the lane
     static_assert(Sh::NSUB_C == 1 && W == 8, "tile-major stores: one sub-DFT per thread");
-    const uint64_t base = (uint64_t)__builtin_amdgcn_readfirstlane(t >> 6) * a.blk_pitch + j0 * W;
-    const uint32_t lane = t & 63;
+    const uint64_t base = (uint64_t)__builtin_amdgcn_readfirstlane(tc >> 6) * a.blk_pitch + j0 * W;
+    const uint32_t lane = tc & 63;
     const uint64_t* ptw = a.post_tw + base;
     uint64_t* o = a.out + (uint64_t)poly * a.out_pitch + base;
     uint64_t tw[C];
@@ -565,12 +690,15 @@ __device__ __forceinline__ void gl_shape_checks() {
 // One tile per workgroup.
 template <int LOGR, int E64, bool FIRST, int TILE, int RG = 0, int CS = 0, int SP = 0>
 // waves per SIMD the VGPR budget allows: 5 where the LDS allows five workgroups and the
-// kernel fits 96 VGPRs without spilling (first passes and the regrouped plan's), else 4
+// kernel fits 96 VGPRs without spilling (first passes and the regrouped plan's), else 4; six
+// for the split exchange of SP 2 (three workgroups of 8 waves per CU, 80 VGPRs)
 __global__ void __launch_bounds__(TILE / 16)
-__attribute__((amdgpu_waves_per_eu((FIRST || RG) && GlShape<LOGR, TILE>::LDS32K ? 5 : 4)))
+__attribute__((amdgpu_waves_per_eu(gl_split(SP) ? 6 : (FIRST || RG) && GlShape<LOGR, TILE>::LDS32K ? 5 : 4)))
 ntt_gl_pass_kernel(GlPassArgs a) {
   gl_shape_checks<LOGR, TILE>();
-  __shared__ __attribute__((aligned(16))) uint64_t lds[GlShape<LOGR, TILE>::LDS];
+  constexpr int LDS64 = GlShape<LOGR, TILE>::LDS / (gl_split(SP) ? 2 : 1);  // 8-B units
+  static_assert(!gl_split(SP) || 3 * LDS64 * 8 <= 160 * 1024, "split exchange: three workgroups per CU");
+  __shared__ __attribute__((aligned(16))) uint64_t lds[LDS64];
   const uint32_t tiles = a.blocks_per_poly * a.batch;
   gl_tile<LOGR, E64, FIRST, TILE, RG, CS, SP>(a, lds, blockIdx.x, tiles, threadIdx.x);
 }

@@ -492,10 +492,15 @@ ForkSet::~ForkSet() {
 // default schedule (measured best at 2^20 x 32): groups of 4 polynomials
 // alternating over the caller's stream and a second one once the batch has at least 8, so the
 // passes of two groups run concurrently and their load / compute / store phases interleave
-// (options ntt.group = polynomials per group, ntt.streams = streams; 0 or >= batch: one group)
-static void gl_schedule(const NttPlan& p, size_t batch, uint32_t split_log, const ForkSet* fork, size_t* G, int* ns) {
+// (options ntt.group = polynomials per group, ntt.streams = streams; 0 or >= batch: one group).
+// The tile-major "10,10" pair (gl_blocked) takes groups of 8 once the batch has 16: its kernels
+// fit three workgroups per CU (ntt_gl.hpp split exchange), and a launch of 4 polynomials is 512
+// workgroups, two per CU: the third slot fills only with 1024 per launch
+static void gl_schedule(const NttPlan& p, size_t batch, bool coset, uint32_t split_log, const ForkSet* fork, size_t* G,
+                        int* ns) {
   const long long go = p.opts.num("ntt.group", -1);
-  *G = go >= 0 ? (size_t)go : (batch >= 8 ? 4 : batch);
+  const size_t dflt = gl_blocked(p, coset, split_log) && batch >= 16 ? 8 : 4;
+  *G = go >= 0 ? (size_t)go : (batch >= 8 ? dflt : batch);
   if (split_log != 0 || *G >= batch) *G = 0;
   *ns = (int)p.opts.num("ntt.streams", 2);
   *ns = *ns < 1 ? 1 : (*ns > GL_MAX_STREAMS ? GL_MAX_STREAMS : *ns);
@@ -505,10 +510,10 @@ static void gl_schedule(const NttPlan& p, size_t batch, uint32_t split_log, cons
 // Polynomials of intermediate scratch that schedule needs. The groups of one stream run one
 // after another, so they share one slot of G polynomials (run_gl_passes): the intermediates of
 // a 2^20 x 32 batch take 64 MiB, not 256 MiB, and stay within the 256 MiB Infinity Cache.
-static size_t gl_scratch_polys(const NttPlan& p, size_t batch, uint32_t split_log, const ForkSet* fork) {
+static size_t gl_scratch_polys(const NttPlan& p, size_t batch, bool coset, uint32_t split_log, const ForkSet* fork) {
   size_t G;
   int ns;
-  gl_schedule(p, batch, split_log, fork, &G, &ns);
+  gl_schedule(p, batch, coset, split_log, fork, &G, &ns);
   return (G == 0 || G * ns > batch) ? batch : G * ns;
 }
 
@@ -516,7 +521,7 @@ static int run_gl_passes(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out
                          DevBuf& s1, hipStream_t stream, uint32_t split_log, ForkSet* fork, const GlCoset* cs) {
   size_t G;
   int ns;
-  gl_schedule(p, batch, split_log, fork, &G, &ns);
+  gl_schedule(p, batch, cs != nullptr, split_log, fork, &G, &ns);
   if (G == 0) return run_gl_group(p, d_in, d_out, batch, s0, s1, stream, split_log, 0, cs);
   // a forward coset transform reads compact polynomials of in_len coefficients
   const size_t in_pitch = (cs && !p.inverse) ? cs->in_len : p.n;
@@ -717,7 +722,7 @@ static int run_plan_impl(const NttPlan& p, const uint64_t* d_in, uint64_t* d_out
     return 0;
   }
   const size_t P = p.logr.size();
-  const size_t bytes = p.gl ? gl_scratch_polys(p, batch, split_log, fork) * gl_scratch_pitch(p, cs != nullptr, split_log) * 8
+  const size_t bytes = p.gl ? gl_scratch_polys(p, batch, cs != nullptr, split_log, fork) * gl_scratch_pitch(p, cs != nullptr, split_log) * 8
                             : batch * p.n * 8;
   int rc = s0.ensure(bytes);
   if (!rc && P > 2) rc = s1.ensure(bytes);
