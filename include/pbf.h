@@ -88,6 +88,8 @@ int pbf_ctx_set_stream(pbf_ctx* ctx, void* stream);
  *                             polynomials, as the reference does (plonk.rs:233-243, 339-370)
  *   prover.timing  1          synchronise at every prover round mark (per-round times)
  *   verifier.vk    0          no verification-key cache
+ *   recover.timing 1          synchronise at every stage mark of the recovery from cells and print
+ *                             the stage's time on stderr (per-stage times)
  * Options are read when used; an ntt* option also drops the context's cached NTT plans (after a
  * device synchronisation), which are rebuilt under the new value. */
 int pbf_ctx_set_option(pbf_ctx* ctx, const char* name, const char* value);
@@ -591,6 +593,71 @@ int pbf_kzg_verify_cells_bn254(pbf_ctx* ctx, const uint64_t* g2, const uint64_t*
                                const uint64_t* omega, size_t n, size_t l, size_t count, const uint64_t* commits,
                                const uint64_t* cell_idx, const uint64_t* ys, const uint64_t* w, const uint64_t* rho,
                                int* ok);
+
+/* ---- Recovery from cells: polynomials from any sufficient set of their KZG cells --------------
+ * What the cells are for: a node that holds only some cells of an extended polynomial (the rest
+ * never sampled, or withheld) rebuilds the polynomial, and from it the missing cells and their
+ * proofs: the recover_cells_and_kzg_proofs of consensus specifications. A call
+ * takes a batch of polynomials that share one pattern of missing cells (the rows of a block that
+ * misses the same columns), so the work on the pattern is paid once per call.
+ * Geometry as for the cell proofs: n and l powers of two, 1 <= l <= n <= 2^27, k = n / l; omega of
+ * order exactly n, as pbf_kzg_verify_cells_bn254 takes it; cell i < k is the l values on
+ * {omega^(i + k t) : t < l}. The unknown polynomials have len coefficients, 1 <= len <= n
+ * (coefficients past len are zero; the usual case is len = n/2, the 2x extension). This version
+ * supports n/l <= 2^16 (more cells: PBF_EINVAL).
+ * Input: count known cells, 1 <= count <= k. cell_idx: count distinct values, each < k, in any
+ *   order; a host pointer in both forms, like the weights of the other KZG entry points.
+ *     cells[(b*count + j)*l + t] = the value of polynomial b at omega^(cell_idx[j] + k t),
+ *   cell-major, the order of out_y of pbf_kzg_open_cells_bn254*: that output feeds this input with
+ *   the missing cells simply left out. One pattern for all batch polynomials, 1 <= batch <= 2^16.
+ *   The call needs count * l >= len (else PBF_EINVAL): below that nothing determines the polynomial.
+ * Output: with R_b the unique polynomial of degree < count*l that takes the given values on the
+ *   known cells,
+ *     out_polys[b*pitch + j], j < len (pitch >= len) = the first len coefficients of R_b, canonical;
+ *     consistent[b] = 1 exactly when every coefficient of R_b from len on is zero: the cells are
+ *       the cells of a polynomial of len coefficients, and that polynomial is the output. With
+ *       count*l == len every input is consistent. With consistent[b] = 0 polynomial b's outputs
+ *       hold canonical values with no further meaning; the other polynomials are unaffected;
+ *     out_y (may be NULL; else batch x n values) = all k cells of the polynomial written to
+ *       out_polys, in the order of out_y of pbf_kzg_open_cells_bn254*: for a consistent input the
+ *       known cells come back bit for bit and the missing ones are filled.
+ *   Results are exact field elements; there is no tolerance anywhere.
+ *   Proofs need no entry point of their own: pbf_kzg_open_cells_bn254_dev on d_out_polys gives every
+ *   cell's proof, the missing cells' included.
+ * Per call: with M the missing cells, Z(x) = prod_{i in M} (x^l - omega^(i l)) and E_b the known
+ *   values with zero on the missing cells, E_b Z = R_b Z on H = <omega> and deg R_b Z < n: one
+ *   batched inverse Fr NTT of size n, the forward transform on the coset 5 H, the pointwise
+ *   division by Z there, the inverse coset transform (three batched transforms of
+ *   pbf_ntt_fr256_batch_dev, the coset's factors 5^j and 5^-j applied by one launch each for the
+ *   whole batch). Z depends on x only through x^l: its k values on H and k on the coset are
+ *   formed once per call, directly as products over M (k |M| products each: hence n/l <= 2^16),
+ *   and the coset's are inverted by the prover's batch inversion. 5^n != 1 for every n <= 2^28,
+ *   so Z has no zero on the coset whatever is missing; the results do not depend on the shift.
+ *   out_y is one more batched forward transform.
+ *   Scratch kept by the context: batch x n x 32 B for the working array (the transforms run in
+ *   place on it) beside the transforms' own, 2k x 32 B for Z, k x 32 B for the inversion, 2k x 4 B
+ *   for the slot and missing-cell tables; the host form also holds its inputs and outputs. The
+ *   powers of the shift, (n + 1) x 32 B per n used, are built at the first call of that n (one
+ *   stream synchronisation) and stay with the context. The power table of (omega, n) is shared
+ *   with pbf_kzg_verify_cells_bn254 and stays until pbf_ctx_release_caches. Nothing about the
+ *   missing set is kept between calls.
+ * Streams: the caller's stream only. The _dev form takes d_cells and every output on the device
+ *   (d_consistent: batch ints) and leaves them there, stream-ordered; omega and cell_idx are on the
+ *   host. The host form returns after its results are on the host, and checks every value of cells
+ *   canonical; the _dev form does not check, like the other _dev forms: values >= r give
+ *   unspecified values, never a fault. Outputs must not overlap inputs.
+ * Errors (PBF_EINVAL, before anything is enqueued or written; never an abort): NULL ctx, omega,
+ *   cell_idx, cells, out_polys or consistent; n or l zero, not a power of two, l > n or n > 2^27;
+ *   n/l > 2^16; omega >= r or not of order exactly n; len = 0 or len > n; count = 0, count > k or
+ *   count * l < len; a cell_idx value >= k or repeated; batch = 0 or batch > 2^16; pitch < len; in
+ *   the host form a cell value >= r.                                                           */
+int pbf_kzg_recover_cells_bn254(pbf_ctx* ctx, const uint64_t* omega, size_t n, size_t l, size_t len, size_t count,
+                                const uint64_t* cell_idx, const uint64_t* cells, size_t batch, uint64_t* out_polys,
+                                size_t pitch, uint64_t* out_y, int* consistent);
+int pbf_kzg_recover_cells_bn254_dev(pbf_ctx* ctx, const uint64_t* omega, size_t n, size_t l, size_t len, size_t count,
+                                    const uint64_t* cell_idx, const uint64_t* d_cells, size_t batch,
+                                    uint64_t* d_out_polys, size_t pitch, uint64_t* d_out_y, int* d_consistent,
+                                    void* stream);
 
 /* Config 5 across G GPUs ("NTT sharded across 8xMI355X"): one process (or thread) per GPU
  * calls pbf_plonk_prove_bn254_sharded_dev with the same inputs (circuit, SRS, challenges,

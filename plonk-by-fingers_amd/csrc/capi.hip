@@ -133,7 +133,7 @@ int pbf_ctx_set_option(pbf_ctx* ctx, const char* name, const char* value) {
                                       "ntt.twsplit", "ntt.no_rg",       "ntt256.maxr",   "ntt256.twlog",
                                       "msm.fx_c",    "g1.mul_base",     "pair.engine",   "pair.lane_wpe",
                                       "prover.pk",   "prover.timing",   "verifier.vk",   "ntt256.l29",
-                                      "g1ntt.tile_log"};
+                                      "g1ntt.tile_log", "recover.timing"};
   bool ok = false;
   for (const char* k : known) ok = ok || strcmp(k, name) == 0;
   if (!ok) return fail(PBF_EINVAL, std::string("unknown option ") + name);

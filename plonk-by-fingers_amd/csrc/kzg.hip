@@ -535,6 +535,13 @@ int cells_open_args(pbf_ctx* ctx, const uint64_t* xext, size_t n, size_t l, cons
 
 }  // namespace
 
+int pbf::cells_ystore_run(const uint64_t* y, uint64_t batch, uint64_t k, uint32_t log_l, uint64_t* out, hipStream_t s) {
+  const uint64_t total = (batch * k) << log_l;
+  hipLaunchKernelGGL(k_cells_ystore, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, y, total, k, log_l, out);
+  PBF_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---------------------------------------------------------------- Poly::eval over Fr
 extern "C" int pbf_poly_eval_fr256(pbf_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64_t* xs, size_t nx,
                                    uint64_t* ys) {
@@ -919,12 +926,7 @@ extern "C" int pbf_kzg_open_cells_bn254_dev(pbf_ctx* ctx, const uint64_t* d_xext
         if ((rc = pbf_ntt_fr256_coset_batch_dev(ctx, om, one, d_polys + 4 * b * pitch, len, y + 4 * b * n, n, 1, 0, s)))
           return rc;
     }
-    if (!direct) {
-      const uint64_t total = (uint64_t)batch * n;
-      hipLaunchKernelGGL(k_cells_ystore, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, (const uint64_t*)y,
-                         total, k, log_l, d_out_y);
-      PBF_HIP(hipGetLastError());
-    }
+    if (!direct && (rc = cells_ystore_run(y, batch, k, log_l, d_out_y, s))) return rc;
   }
   if (len <= l) {  // degree below l: every quotient is zero, every W the identity (k = 1 included)
     PBF_HIP(hipMemsetAsync(d_out_w, 0, k * 64, s));

@@ -89,6 +89,10 @@ int g1_ntt_run(pbf_ctx* ctx, const U256& wm, const uint64_t* d_in, uint64_t* d_o
 // inverse transform. w from g1_work(ctx, n, n, .).
 int g1_mul_xyzz_run(const G1Work& w, const uint64_t* d_points, const uint64_t* d_scalars, uint64_t n, hipStream_t s);
 
+// kzg.hip: the cell-major store of the cell proofs, shared with the recovery (kzg_recover.hip):
+// out[(b k + i) l + t] = y[b n + i + k t] for `batch` transforms of size n = k l (k_cells_ystore)
+int cells_ystore_run(const uint64_t* y, uint64_t batch, uint64_t k, uint32_t log_l, uint64_t* out, hipStream_t s);
+
 // verify.hip: Plonk::verify's preprocessing, shared by the single and the batched verifier:
 // pre = the commitments of q_m q_l q_r q_o q_c s_sigma_1..3 (canonical affine), from the
 // context's verification key when option verifier.vk allows and q, copies and the SRS equal

@@ -143,6 +143,10 @@ SIGNATURES = [
                                                     _vp]),
     ("pbf_kzg_verify_cells_bn254", ctypes.c_int, [_vp, _p64, _p64, _sz, _p64, _sz, _sz, _sz, _p64, _p64, _p64, _p64,
                                                   _p64, ctypes.POINTER(ctypes.c_int)]),
+    ("pbf_kzg_recover_cells_bn254", ctypes.c_int, [_vp, _p64, _sz, _sz, _sz, _sz, _p64, _p64, _sz, _p64, _sz, _p64,
+                                                   ctypes.POINTER(ctypes.c_int)]),
+    ("pbf_kzg_recover_cells_bn254_dev", ctypes.c_int, [_vp, _p64, _sz, _sz, _sz, _sz, _p64, _vp, _sz, _vp, _sz, _vp,
+                                                       _vp, _vp]),
 ]
 
 _lib = None
@@ -750,6 +754,42 @@ class Context:
                                                    _ptr(_g1_limbs([e[3] for e in entries])),
                                                    _ptr(ints_to_limbs(list(rhos))), ctypes.byref(ok)))
         return ok.value == 1
+
+    # ---- recovery from cells (include/pbf.h "Recovery from cells"; kzg_recover.hip)
+    def kzg_recover_cells(self, omega: int, n: int, l: int, length: int, cell_idx, cells, pitch: int | None = None,
+                          with_y: bool = True):
+        """pbf_kzg_recover_cells_bn254: cells[b][j] the l values of cell cell_idx[j] of polynomial b.
+        (polys, ys or None, consistent): polys[b] the `length` coefficients, ys[b][i] the l values of
+        cell i < n / l, consistent[b] 1 when the cells are those of a polynomial of `length`
+        coefficients."""
+        batch, count = len(cells), len(cell_idx)
+        if any(len(c) != count for c in cells) or any(len(v) != l for c in cells for v in c):
+            raise ValueError("one list of l values per known cell and polynomial")
+        pitch = length if pitch is None else int(pitch)
+        k = n // l if l else 0
+        a = ints_to_limbs([v for c in cells for cell in c for v in cell]) if batch * count * l else np.zeros(4, np.uint64)
+        out = np.zeros(4 * max(batch * max(pitch, length), 1), dtype=np.uint64)
+        ys = np.zeros(4 * max(batch * n, 1), dtype=np.uint64)
+        flags = np.zeros(max(batch, 1), dtype=np.int32)
+        _check(self.lib.pbf_kzg_recover_cells_bn254(self.h, _ptr(ints_to_limbs([omega])), n, l, length, count,
+                                                    _ptr(_as_u64(list(cell_idx) or [0])), _ptr(a), batch, _ptr(out),
+                                                    pitch, _ptr(ys) if with_y else None,
+                                                    flags.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        p, v = limbs_to_ints(out), limbs_to_ints(ys)
+        polys = [p[b * pitch:b * pitch + length] for b in range(batch)]
+        got = [[v[(b * k + i) * l:(b * k + i + 1) * l] for i in range(k)] for b in range(batch)]
+        return polys, (got if with_y else None), [int(f) for f in flags[:batch]]
+
+    def kzg_recover_cells_dev(self, omega: int, n: int, l: int, length: int, cell_idx, d_cells: int, batch: int,
+                              d_out_polys: int, pitch: int, d_out_y: int, d_consistent: int, stream: int = 0) -> None:
+        """The same on the device: d_out_polys (batch x pitch), d_out_y (batch x n values, cell-major,
+        or 0 for none) and d_consistent (batch ints) are written on stream and stay there; cell_idx
+        is a host list."""
+        _check(self.lib.pbf_kzg_recover_cells_bn254_dev(self.h, _ptr(ints_to_limbs([omega])), n, l, length,
+                                                        len(cell_idx), _ptr(_as_u64(list(cell_idx) or [0])),
+                                                        _vp(d_cells), batch, _vp(d_out_polys), pitch,
+                                                        _vp(d_out_y) if d_out_y else None, _vp(d_consistent),
+                                                        _vp(stream) if stream else None))
 
     def plonk_prove_bn254_sharded_dev(self, comm: "Comm", n, d_q, d_copies, d_abc, chal, rnd, d_srs, srs_m,
                                       k1k2=(2, 3), mode=0, stream: int = 0):
