@@ -22,34 +22,26 @@
 //   k_rec_flag      the factors g^-j, the first len coefficients to the caller, and consistent_b =
 //                   no coefficient from len on is non-zero
 //   out_y           one more forward transform, of what k_rec_flag left in the working array, and
-//                   the cell-major store of the cell proofs (kzg.hip cells_ystore_run)
+//                   the cell-major store of the cell proofs (kzg_cells.hip cells_ystore_run)
 // g = 5: 5^(2^28) != 1 in Fr (tests/test_recover_expect.py), so g^n != 1 for every n <= 2^27, hence
 // g^l c_m is no k-th root of unity and Z has no zero on g H whatever is missing.
 //
 // Conversion-free like the rest of the KZG code: canonical values times Montgomery-form multipliers
 // are canonical products. A chain of m products of canonical factors loses R^m, which the chain's
 // first operand carries in advance.
-#include <algorithm>
 #include <cstdio>
 #include <ctime>
 #include <string>
-#include <vector>
-#include "../../include/pbf.h"
-#include "prover.hpp"
+#include "kzg.hpp"
 
 using namespace pbf;
 
 namespace {
 
-constexpr size_t REC_MAX_N = (size_t)1 << 27, REC_MAX_K = (size_t)1 << 16, REC_MAX_BATCH = (size_t)1 << 16;
+constexpr size_t REC_MAX_K = (size_t)1 << 16, REC_MAX_BATCH = (size_t)1 << 16;
 constexpr uint32_t REC_NONE = 0xffffffffu;  // the slot of a missing cell
 constexpr uint64_t REC_SHIFT = 5;           // g
 constexpr uint32_t REC_LANES = 1u << 16;    // k_rec_zvals splits M until 2k values fill this many lanes
-
-// omega^e canonical, e < n, from the domain table of (omega, n); n = 1 has no table
-__device__ __forceinline__ U256 rec_pow(const uint64_t* tw, uint64_t n, uint64_t e) {
-  return n > 1 ? fr_domain_at(tw, n, e) : Fr::one_plain();
-}
 
 // z[m] = Z at y = c_m in Montgomery form for m < k, z[k + m] = Z at y = g^l c_m canonical: the
 // product over the nmiss missing cells of (y - c_i). A workgroup takes 256 >> log_p values of y,
@@ -67,13 +59,13 @@ __global__ void __launch_bounds__(256) k_rec_zvals(const uint64_t* tw, uint64_t 
   const bool live = m < 2 * (uint64_t)k;
   U256 y = u256_zero();
   if (live) {
-    y = rec_pow(tw, n, (m & (k - 1)) << log_l);
+    y = fr_domain_pow(tw, n, (m & (k - 1)) << log_l);
     if (m >= k) y = Fr::mul(gl, y);
   }
   U256 acc = p ? fr_one_m() : (m < k ? start_h : start_c);
   for (uint32_t r0 = 0; r0 < nmiss; r0 += 256) {
     __syncthreads();  // the previous tile's readers are done with sh
-    if (r0 + t < nmiss) sh[t] = rec_pow(tw, n, (uint64_t)miss[r0 + t] << log_l);
+    if (r0 + t < nmiss) sh[t] = fr_domain_pow(tw, n, (uint64_t)miss[r0 + t] << log_l);
     __syncthreads();
     const uint32_t cnt = min(256u, nmiss - r0);
     for (uint32_t r = p; r < cnt; r += 1u << log_p) acc = Fr::mul(acc, Fr::sub(y, sh[r]));
@@ -177,28 +169,26 @@ int rec_args(pbf_ctx* ctx, const uint64_t* omega, size_t n, size_t l, size_t len
              const uint64_t* cell_idx, const uint64_t* cells, size_t batch, const uint64_t* out_polys, size_t pitch,
              const int* consistent, RecGeom* g) {
   if (!ctx || !omega || !cell_idx || !cells || !out_polys || !consistent) return fail(PBF_EINVAL, "null argument");
-  if (n == 0 || (n & (n - 1)) || n > REC_MAX_N) return fail(PBF_EINVAL, "n must be a power of two in 1 .. 2^27");
-  if (l == 0 || (l & (l - 1)) || l > n) return fail(PBF_EINVAL, "l must be a power of two in 1 .. n");
+  int rc = kzg_n_check(n);
+  if (rc || (rc = kzg_l_check(n, l, &g->log_l))) return rc;
   const size_t k = n / l;
   if (k > REC_MAX_K) return fail(PBF_EINVAL, "n / l must be at most 2^16");
-  int rc = fr_domain_check(omega, n, &g->wm);
-  if (rc) return rc;
+  if ((rc = fr_domain_check(omega, n, &g->wm))) return rc;
   if (len == 0 || len > n) return fail(PBF_EINVAL, "len must be in 1 .. n");
   if (count == 0 || count > k) return fail(PBF_EINVAL, "count must be in 1 .. n / l");
   if (count * l < len) return fail(PBF_EINVAL, "count * l must be at least len");
   if (batch == 0 || batch > REC_MAX_BATCH) return fail(PBF_EINVAL, "batch must be in 1 .. 2^16");
   if (pitch < len) return fail(PBF_EINVAL, "pitch shorter than len");
+  if ((rc = kzg_idx_check(cell_idx, count, k))) return rc;
   g->tab.assign(k, REC_NONE);
   for (size_t j = 0; j < count; ++j) {
     const uint64_t i = cell_idx[j];
-    if (i >= k) return fail(PBF_EINVAL, "cell_idx must be below n / l");
     if (g->tab[i] != REC_NONE) return fail(PBF_EINVAL, "cell_idx must be distinct");
     g->tab[i] = (uint32_t)j;
   }
   for (size_t i = 0; i < k; ++i)
     if (g->tab[i] == REC_NONE) g->tab.push_back((uint32_t)i);
   while (((size_t)1 << g->log_n) < n) ++g->log_n;
-  while (((size_t)1 << g->log_l) < l) ++g->log_l;
   return 0;
 }
 

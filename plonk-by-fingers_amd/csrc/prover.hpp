@@ -1,7 +1,8 @@
-// What prover.hip exports to the KZG entry points (kzg.hip) and the verifiers (verify.hip,
+// What prover.hip exports to the KZG units (through kzg.hpp) and the verifiers (verify.hip,
 // verify_batch.hip): the geometry of the blocked synthetic division and host launchers of the
 // prover's own kernels (chunked Horner evaluation, linear combination, k_hs1..3, the H powers and
-// sigma labels). Plonk::prove goes through the same launchers.
+// sigma labels). Plonk::prove goes through the same launchers. Then what g1_ntt.hip, g1_mul.hip
+// and verify.hip export to the same users, and two device helpers over Fr.
 #pragma once
 #include "fr_host.hpp"
 #include "msm.hpp"
@@ -60,8 +61,21 @@ __device__ __forceinline__ U256 fr_domain_at(const uint64_t* tw, uint64_t n, uin
   const U256 w = u256_from_u64(tw + 4 * (i & (h - 1)));
   return i < h ? w : Fr::sub(u256_zero(), w);
 }
+// The workgroup's sum of v over its blockDim.x lanes (a power of two; sh: as many values), valid
+// on lane 0. The leading barrier lets a kernel call it again on the same sh, as k_ev_dot does.
+__device__ __forceinline__ U256 fr_block_sum(U256* sh, const U256& v) {
+  const uint32_t t = threadIdx.x;
+  __syncthreads();
+  sh[t] = v;
+  __syncthreads();
+  for (uint32_t s = blockDim.x / 2; s; s >>= 1) {
+    if (t < s) sh[t] = Fr::add(sh[t], sh[t + s]);
+    __syncthreads();
+  }
+  return sh[0];
+}
 
-// g1_ntt.hip: the pieces of the G1 NTT that FK20 (kzg.hip) strings together without leaving Xyzz.
+// g1_ntt.hip: the pieces of the G1 NTT that FK20 (kzg_cells.hip) strings together without leaving Xyzz.
 // The context's scratch: x, `points` Xyzz (absent with points = 0), and the window table for
 // launches of up to min(`products`, 2^g1ntt.tile_log) products, `stride` of them.
 struct G1Work {
@@ -88,10 +102,6 @@ int g1_ntt_run(pbf_ctx* ctx, const U256& wm, const uint64_t* d_in, uint64_t* d_o
 // affine points times n canonical scalars, left as Xyzz where g1_ntt_stages reads the input of an
 // inverse transform. w from g1_work(ctx, n, n, .).
 int g1_mul_xyzz_run(const G1Work& w, const uint64_t* d_points, const uint64_t* d_scalars, uint64_t n, hipStream_t s);
-
-// kzg.hip: the cell-major store of the cell proofs, shared with the recovery (kzg_recover.hip):
-// out[(b k + i) l + t] = y[b n + i + k t] for `batch` transforms of size n = k l (k_cells_ystore)
-int cells_ystore_run(const uint64_t* y, uint64_t batch, uint64_t k, uint32_t log_l, uint64_t* out, hipStream_t s);
 
 // verify.hip: Plonk::verify's preprocessing, shared by the single and the batched verifier:
 // pre = the commitments of q_m q_l q_r q_o q_c s_sigma_1..3 (canonical affine), from the

@@ -189,18 +189,7 @@ __global__ void __launch_bounds__(64) k_vb_scalars(const uint64_t* __restrict__ 
   stm(c + 8 * cs, Fr::sub(zero, fmul(rho, ecoef)));  // - E
 }
 
-// canonical residues add like any others: no Montgomery conversion in the sums
-__device__ __forceinline__ U256 block_sum(U256 acc, U256* sh) {
-  const uint32_t t = threadIdx.x;
-  sh[t] = acc;
-  __syncthreads();
-  for (uint32_t w = blockDim.x / 2; w; w >>= 1) {
-    if (t < w) sh[t] = Fr::add(sh[t], sh[t + w]);
-    __syncthreads();
-  }
-  return sh[0];
-}
-
+// canonical residues add like any others: no Montgomery conversion in the sums (fr_block_sum)
 // part[j][b] = sum of contrib[j][i] over this block's share of [lo, hi); grid (nb <= VB_PART, 9)
 __global__ void __launch_bounds__(256) k_vb_colsum(const uint64_t* contrib, uint32_t count, uint32_t lo, uint32_t hi,
                                                    uint64_t* part) {
@@ -209,7 +198,7 @@ __global__ void __launch_bounds__(256) k_vb_colsum(const uint64_t* contrib, uint
   U256 acc = u256_zero();
   for (uint64_t i = (uint64_t)lo + blockIdx.x * 256u + threadIdx.x; i < hi; i += (uint64_t)gridDim.x * 256u)
     acc = Fr::add(acc, u256_from_u64(contrib + 4 * ((uint64_t)j * count + i)));
-  acc = block_sum(acc, sh);
+  acc = fr_block_sum(sh, acc);
   if (threadIdx.x == 0) u256_to_u64(acc, part + 4 * ((uint64_t)j * VB_PART + blockIdx.x));
 }
 
@@ -219,7 +208,7 @@ __global__ void __launch_bounds__(64) k_vb_colsum2(const uint64_t* part, uint32_
   const uint32_t j = blockIdx.x;
   U256 acc = u256_zero();
   if (threadIdx.x < nb) acc = u256_from_u64(part + 4 * ((uint64_t)j * VB_PART + threadIdx.x));
-  acc = block_sum(acc, sh);
+  acc = fr_block_sum(sh, acc);
   if (threadIdx.x == 0) u256_to_u64(acc, out + 4 * j);
 }
 

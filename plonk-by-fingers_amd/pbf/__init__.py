@@ -598,7 +598,7 @@ class Context:
                                              _ptr(ints_to_limbs(list(rhos))), ctypes.byref(ok)))
         return ok.value == 1
 
-    # ---- KZG in evaluation form (include/pbf.h "KZG in evaluation form"; g1_ntt.hip, kzg.hip)
+    # ---- KZG in evaluation form (include/pbf.h "KZG in evaluation form"; g1_ntt.hip, kzg_evals.hip)
     def ntt_g1(self, omega: int, points, inverse: bool = False) -> list:
         """pbf_ntt_g1_bn254: out[k] = sum_j [omega^(jk)] points[j] (the inverse: omega^-1 and
         n^-1); points as (x, y), the identity (0, 0). The points are checked on the curve."""
@@ -644,7 +644,7 @@ class Context:
                                                      _vp(stream) if stream else None))
         return limbs_to_ints(ys)[:batch], self._points(w)[0]
 
-    # ---- every opening at once (include/pbf.h "Every opening at once"; g1_mul.hip, kzg.hip)
+    # ---- every opening at once (include/pbf.h "Every opening at once"; g1_mul.hip, kzg_cells.hip)
     def g1_mul(self, points, scalars) -> list:
         """pbf_g1_bn254_mul: [[k_i] P_i]; points as (x, y), the identity (0, 0). Points are
         checked on the curve and scalars < r."""
@@ -696,7 +696,7 @@ class Context:
                                                    _vp(d_out_y) if d_out_y else None, _vp(d_out_w),
                                                    _vp(stream) if stream else None))
 
-    # ---- cell proofs (include/pbf.h "KZG cell proofs"; kzg.hip)
+    # ---- cell proofs (include/pbf.h "KZG cell proofs"; kzg_cells.hip)
     def kzg_cells_setup(self, srs, n: int, l: int, omega2: int) -> list:
         """pbf_kzg_cells_setup_bn254: the 2n points xext of (srs, n, l), slab-major, for omega2 of
         order 2n."""

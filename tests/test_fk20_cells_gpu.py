@@ -1,4 +1,4 @@
-"""KZG cell proofs (csrc/kzg.hip pbf_kzg_cells_setup_bn254*, pbf_kzg_open_cells_bn254*,
+"""KZG cell proofs (csrc/kzg_cells.hip pbf_kzg_cells_setup_bn254*, pbf_kzg_open_cells_bn254*,
 pbf_kzg_verify_cells_bn254), bit-exact: no tolerance anywhere.
 
 Expected values use the trapdoor S of the test SRS (tests/fk20_cells_expect.py): xext =
@@ -407,6 +407,49 @@ def test_verify_rejects(ctx, world, proven):
     srs = list(proven.srs)
     srs[l - 1] = off
     assert not ctx.kzg_verify_cells(proven.g2s, srs, proven.omega, proven.n, l, good, rhos)
+
+
+def cyclic_entries(proven, count):
+    """count entries: the cells of both polynomials, repeated cyclically"""
+    return [proven.entry(j % 2, (j // 2) % proven.k) for j in range(count)]
+
+
+def with_changed_value(entry, t=0):
+    c, i, ys, w = entry
+    bad_ys = list(ys)
+    bad_ys[t] = (bad_ys[t] + 1) % R
+    return (c, i, bad_ys, w)
+
+
+only_64x8 = pytest.mark.parametrize("proven", [(64, 8)], indirect=True, ids=["64x8"])
+
+
+@only_64x8
+@pytest.mark.parametrize("count", [32, 33, 257])
+def test_verify_accepts_many_entries(ctx, proven, count):
+    """32 entries fill one chunk of k_cells_vsweep (CV_CH), 33 leave one entry alone in a second
+    chunk, so that k_cells_vsum adds two; 257 are two workgroups of k_cells_vprep, one live lane in
+    the second, and nine chunks."""
+    assert proven.verify(ctx, cyclic_entries(proven, count))
+
+
+@only_64x8
+@pytest.mark.parametrize("count,pos", [(33, 32), (257, 256)])
+def test_verify_rejects_a_changed_value_in_the_last_entry(ctx, proven, count, pos):
+    good, rhos = cyclic_entries(proven, count), proven.rhos(count)
+    bad = list(good)
+    bad[pos] = with_changed_value(good[pos], proven.l - 1)
+    assert not proven.verify(ctx, bad, rhos)
+    assert proven.verify(ctx, good, rhos)
+
+
+@only_64x8
+def test_verify_rejects_an_off_curve_w_in_the_second_workgroup(ctx, proven):
+    good, rhos = cyclic_entries(proven, 257), proven.rhos(257)
+    c, i, ys, w = good[256]
+    off = (w[0], (w[1] + 1) % F.Q)
+    assert not F.g1_on_curve(off)
+    assert not proven.verify(ctx, good[:256] + [(c, i, ys, off)], rhos)
 
 
 def test_equal_rho_lets_errors_cancel(ctx, proven):

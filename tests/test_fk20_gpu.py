@@ -1,4 +1,4 @@
-"""Every opening at once (csrc/kzg.hip pbf_kzg_fk20_setup_bn254*, pbf_kzg_open_all_bn254*),
+"""Every opening at once (csrc/kzg_cells.hip pbf_kzg_fk20_setup_bn254*, pbf_kzg_open_all_bn254*),
 bit-exact: no tolerance anywhere.
 
 Expected values use the trapdoor S of the test SRS (tests/fk20_expect.py): xext = [NTT_2n(a)]G,

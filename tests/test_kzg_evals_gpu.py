@@ -1,4 +1,4 @@
-"""KZG in evaluation form (csrc/kzg.hip pbf_kzg_open_evals_bn254*, commit against the Lagrange
+"""KZG in evaluation form (csrc/kzg_evals.hip pbf_kzg_open_evals_bn254*, commit against the Lagrange
 SRS of csrc/g1_ntt.hip), bit-exact: no tolerance anywhere.
 
 Expected values use the trapdoor S of the test SRS, as tests/test_kzg_gpu.py: commit(p) = [p(S)]G,

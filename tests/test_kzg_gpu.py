@@ -311,6 +311,25 @@ def test_verify_rejects_a_tampered_entry(ctx, world, openings, kind):
     assert ctx.kzg_verify(world.g2s, ents, rhos) is True
 
 
+@pytest.mark.parametrize("count", [256, 257])
+def test_verify_accepts_across_workgroups(ctx, world, openings, count):
+    """256 entries fill one workgroup of k_kzg_vprep; 257 are two workgroups with one live lane in
+    the second, and two partial sums for k_kzg_vsum."""
+    ents, rhos = openings.take(count)
+    assert ctx.kzg_verify(world.g2s, ents, rhos) is True
+
+
+@pytest.mark.parametrize("pos", [255, 256])
+def test_verify_rejects_a_tampered_y_across_workgroups(ctx, world, openings, pos):
+    """y reaches the verdict only through the partial sums of rho_i y_i: the last lane of the first
+    workgroup and the only live lane of the second."""
+    ents, rhos = openings.take(257)
+    bad = list(ents)
+    bad[pos] = _tamper(ents[pos], "y")
+    assert ctx.kzg_verify(world.g2s, bad, rhos) is False
+    assert ctx.kzg_verify(world.g2s, ents, rhos) is True
+
+
 def test_verify_accepts_the_identity_as_an_opening(ctx, world):
     z = 12345
     (c,) = ctx.kzg_commit(world.srs[:1], [[7]])
