@@ -423,6 +423,17 @@ int pbf_kzg_verify_bn254(pbf_ctx* ctx, const uint64_t* g2, size_t count, const u
  *   by a full-width scalar (the inverse: n more), on a 4-bit fixed window. The
  *   context keeps the table of omega's powers per (omega, n) until pbf_ctx_release_caches, and
  *   n x 128 B of scratch plus the window table of option g1ntt.tile_log.
+ * pbf_ntt_g1_bn254_batch*: `batch` transforms of size n under the same omega in one call,
+ *   transform b at in + 8*b*n and out + 8*b*n (u64 words; the layout is compact); in == out is
+ *   allowed. Each transform is, bit for bit, what pbf_ntt_g1_bn254* returns for that slice, and
+ *   the single forms are batch = 1 of this one. Limits: 1 <= batch and n * batch <= 2^28, the
+ *   scratch of the largest single transform. The host form checks every point of every transform;
+ *   the _dev form does not, like its single twin. Cost: batch times the products of the single
+ *   transform, in batch times fewer launches: a stage is ceil(batch n/2 / 2^g1ntt.tile_log)
+ *   launches, and a launch costs the latency of one window product however few lanes it carries,
+ *   so small transforms are far cheaper by the batch than one by one. Scratch:
+ *   n * batch x 128 B plus the window table (min(n * batch / 2, 2^tile_log) x 1920 B; the inverse:
+ *   n * batch).
  * Commit from evaluations needs no entry point of its own:
  *     pbf_kzg_commit_bn254*(lsrs, n, evals, n, pitch, batch, out) = [p_b(s)]G,
  *   the same points as the commitments of the coefficient forms against srs, and
@@ -445,10 +456,15 @@ int pbf_kzg_verify_bn254(pbf_ctx* ctx, const uint64_t* g2, size_t count, const u
  *   device, everything else on the host; caller's stream only).
  * Errors (PBF_EINVAL, before anything is enqueued): those of pbf_kzg_open_bn254* with len read as
  *   n; n = 0, not a power of two or above 2^28; omega >= r or not of order exactly n; NULL
- *   pointers; in the host form of the NTT a coordinate >= q or a point off the curve.           */
+ *   pointers; in the host form of the NTT a coordinate >= q or a point off the curve (of any
+ *   transform of a batch); batch = 0 or n * batch > 2^28. Nothing is enqueued or written.       */
 int pbf_ntt_g1_bn254(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* in, uint64_t* out, size_t n, int inverse);
 int pbf_ntt_g1_bn254_dev(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* d_in, uint64_t* d_out, size_t n,
                          int inverse, void* stream);
+int pbf_ntt_g1_bn254_batch(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* in, uint64_t* out, size_t n,
+                           size_t batch, int inverse);
+int pbf_ntt_g1_bn254_batch_dev(pbf_ctx* ctx, const uint64_t* omega, const uint64_t* d_in, uint64_t* d_out, size_t n,
+                               size_t batch, int inverse, void* stream);
 int pbf_kzg_open_evals_bn254(pbf_ctx* ctx, const uint64_t* lsrs, size_t n, const uint64_t* omega,
                              const uint64_t* evals, size_t pitch, size_t batch, const uint64_t* z,
                              const uint64_t* weights, uint64_t* out_y, uint64_t* out_w);
@@ -532,17 +548,18 @@ int pbf_kzg_open_all_bn254_dev(pbf_ctx* ctx, const uint64_t* d_xext, size_t n, c
  *     xext[r*2k + i] = G1-NTT_{2k, omega2^l}(a_r)[i],  r < l, i < 2k   (canonical affine, slab-major),
  *   so a caller may also compute or store it. Needs srs_m >= n - l (points 0 .. n-l-1 are read).
  *   With l = 1 the output equals that of pbf_kzg_fk20_setup_bn254* bit for bit; with l = n every
- *   point is the identity. The l transforms run one after another on the G1 NTT. The host form
- *   checks the points it reads; d_xext must not overlap d_srs.
+ *   point is the identity. The l transforms run as one batch of the G1 NTT
+ *   (pbf_ntt_g1_bn254_batch_dev: batch = l, size 2k, in place). The host form checks the points it
+ *   reads; d_xext must not overlap d_srs.
  * pbf_kzg_open_cells_bn254*: polynomials, pitch, batch and the host weights exactly as
  *   pbf_kzg_open_all_bn254* takes them, 1 <= len <= n:
  *     out_w[i] = W_i of c = sum_b weights_b p_b, i < k   (k points),
  *     out_y[(b*k + i)*l + t] = p_b(omega^(i + k t))      (batch x n values, cell-major: the l
  *                values of a cell are consecutive, in the order the verifier takes them;
  *                out_y may be NULL).
- *   Per call: c = (2k)^-1 sum_b weights_b p_b (the inverse transform's factor rides on the
- *   weights), bhat_r = the Fr NTT of size 2k, root omega2^l, of b_r, all l in one batch; the 2n
- *   products [bhat_(r,i)] xext_(r,i) as one vector; chat_i = their sum over r < l, written where
+ *   Per call: c = sum_b weights_b p_b, its b_r gathered times (2k)^-1 (the inverse transform's
+ *   factor rides on them), bhat_r = the Fr NTT of size 2k, root omega2^l, of b_r, all l in one
+ *   batch; the 2n products [bhat_(r,i)] xext_(r,i) as one vector; chat_i = their sum over r < l, written where
  *   the unscaled inverse G1 NTT of size 2k reads it; then the forward one of size k over entries
  *   k-1 .. 2k-2 of its result: 2n + k log2 k + k/2 (log2 k - 1) window products, 2k (l - 1)
  *   additions and one affine conversion per output point, nothing leaving Xyzz in between. The
@@ -553,6 +570,28 @@ int pbf_kzg_open_all_bn254_dev(pbf_ctx* ctx, const uint64_t* d_xext, size_t n, c
  *   g1ntt.tile_log, 2n x 32 B for bhat, n x 32 B for the b_r, len x 32 B for c and, with out_y and
  *   1 < l < n, batch x n x 32 B; the power tables of omega2^l, omega^l and omega stay until
  *   pbf_ctx_release_caches.
+ * pbf_kzg_open_cells_each_bn254*: the proofs of EACH polynomial of a batch in one call (a block
+ *   builder's rows, or the rows pbf_kzg_recover_cells_bn254_dev has just recovered): xext, n, l,
+ *   omega2, polys, len, pitch and the streams exactly as pbf_kzg_open_cells_bn254* takes them, and
+ *   no weights:
+ *     out_w[b*k + i] = W_i of p_b, i < k, b < batch      (batch x k points, polynomial-major),
+ *   for every b bit for bit the out_w of pbf_kzg_open_cells_bn254* called on polynomial b alone
+ *   with weight 1; out_y is exactly that entry point's out_y (batch x n values, cell-major; may be
+ *   NULL). With l = 1 it is every opening of every polynomial (pbf_kzg_open_all_bn254* per
+ *   polynomial); with len <= l every W is the identity. This version supports 1 <= batch <= 2^16
+ *   and batch * n <= 2^24 (more: PBF_EINVAL; a caller with more rows loops).
+ *   Per call: the steps of pbf_kzg_open_cells_bn254* with every vector batch times as long: one
+ *   gather that also applies (2k)^-1, one batched Fr NTT of size 2k over batch x l rows, the
+ *   batch x 2n products [bhat_(b,r,i)] xext_(r,i) as ONE vector (a launch takes 2^g1ntt.tile_log
+ *   of them whatever 2n is: polynomials share a launch, and a launch may split a polynomial), the
+ *   sums over r into batch x 2k slots, and the two transforms as batches of the G1 NTT over
+ *   `batch` transforms: batch x (2n + k log2 k + k/2 (log2 k - 1)) window products, one affine
+ *   conversion per output point, nothing leaving Xyzz in between. The transforms' 2 log2 k + 1
+ *   stages are paid once per call, not once per polynomial.
+ *   Scratch kept by the context: batch x (2n + 2k) x 128 B of points (every product is kept until
+ *   the sums are formed: 4 GiB at batch * n = 2^24) plus the window table of option
+ *   g1ntt.tile_log, batch x 2n x 32 B for bhat, batch x n x 32 B for the b_r and, with out_y and
+ *   1 < l < n, batch x n x 32 B.
  * pbf_kzg_verify_cells_bn254: host pointers, like pbf_kzg_verify_bn254. g2 = [G2, [s^l]G2]: the
  *   caller brings the l-th power of s on the twist, not [s]G2 (a trusted setup publishes it; tests
  *   make it from a trapdoor with pbf_g2_bn254_mul). srs = the first l G1 points, srs_m >= l; omega
@@ -578,7 +617,9 @@ int pbf_kzg_open_all_bn254_dev(pbf_ctx* ctx, const uint64_t* d_xext, size_t n, c
  * Errors (PBF_EINVAL, before anything is enqueued; never an abort): those of
  *   pbf_kzg_open_all_bn254* and pbf_kzg_verify_bn254; l = 0, not a power of two or above n; a short
  *   SRS (srs_m < n - l for the setup, srs_m < l for the verifier); cell_idx >= k; count * l > 2^22;
- *   omega not of order exactly n (omega2: 2n); a value of ys >= r.                               */
+ *   omega not of order exactly n (omega2: 2n); a value of ys >= r; for
+ *   pbf_kzg_open_cells_each_bn254* those of pbf_kzg_open_cells_bn254* without the weights, and
+ *   batch * n > 2^24.                                                                           */
 int pbf_kzg_cells_setup_bn254(pbf_ctx* ctx, const uint64_t* srs, size_t srs_m, const uint64_t* omega2, size_t n,
                               size_t l, uint64_t* xext);
 int pbf_kzg_cells_setup_bn254_dev(pbf_ctx* ctx, const uint64_t* d_srs, size_t srs_m, const uint64_t* omega2, size_t n,
@@ -589,6 +630,12 @@ int pbf_kzg_open_cells_bn254(pbf_ctx* ctx, const uint64_t* xext, size_t n, size_
 int pbf_kzg_open_cells_bn254_dev(pbf_ctx* ctx, const uint64_t* d_xext, size_t n, size_t l, const uint64_t* omega2,
                                  const uint64_t* d_polys, size_t len, size_t pitch, size_t batch,
                                  const uint64_t* weights, uint64_t* d_out_y, uint64_t* d_out_w, void* stream);
+int pbf_kzg_open_cells_each_bn254(pbf_ctx* ctx, const uint64_t* xext, size_t n, size_t l, const uint64_t* omega2,
+                                  const uint64_t* polys, size_t len, size_t pitch, size_t batch, uint64_t* out_y,
+                                  uint64_t* out_w);
+int pbf_kzg_open_cells_each_bn254_dev(pbf_ctx* ctx, const uint64_t* d_xext, size_t n, size_t l,
+                                      const uint64_t* omega2, const uint64_t* d_polys, size_t len, size_t pitch,
+                                      size_t batch, uint64_t* d_out_y, uint64_t* d_out_w, void* stream);
 int pbf_kzg_verify_cells_bn254(pbf_ctx* ctx, const uint64_t* g2, const uint64_t* srs, size_t srs_m,
                                const uint64_t* omega, size_t n, size_t l, size_t count, const uint64_t* commits,
                                const uint64_t* cell_idx, const uint64_t* ys, const uint64_t* w, const uint64_t* rho,

@@ -33,15 +33,16 @@ __global__ void __launch_bounds__(GN_T) __attribute__((amdgpu_waves_per_eu(2))) 
   st_affine(out + 8 * i, p);
 }
 
-// the same, left as Xyzz at x[bitrev((n - i) mod n)]: no inversion
+// the same, left as Xyzz at x[bitrev((n - i) mod n)]: no inversion. Past n the vector goes on with
+// the next set of n scalars over the same n points, into the next n of x (FK20 of a batch)
 __global__ void __launch_bounds__(GN_T) __attribute__((amdgpu_waves_per_eu(2))) k_g1_mul_x(const uint64_t* pts, const uint64_t* sc, Xyzz* x, Xyzz* tbl,
                                                    uint64_t stride, uint64_t i0, uint64_t count, uint64_t n,
                                                    uint32_t log_n) {
   const uint64_t t = (uint64_t)blockIdx.x * GN_T + threadIdx.x;
   if (t >= count) return;
-  const uint64_t i = i0 + t;
-  const Xyzz p = g1_mul_win(ld_affine(pts + 8 * i), (const uint32_t*)(sc + 4 * i), tbl + t, stride);
-  st_pt(x + (__brevll((n - i) & (n - 1)) >> (64 - log_n)), p);
+  const uint64_t i = i0 + t, m = i & (n - 1);
+  const Xyzz p = g1_mul_win(ld_affine(pts + 8 * m), (const uint32_t*)(sc + 4 * i), tbl + t, stride);
+  st_pt(x + (i - m) + (__brevll((n - m) & (n - 1)) >> (64 - log_n)), p);
 }
 
 uint32_t blocks_of(uint64_t threads, uint32_t per) { return (uint32_t)((threads + per - 1) / per); }
@@ -70,11 +71,13 @@ int mul_args(pbf_ctx* ctx, const uint64_t* points, const uint64_t* scalars, cons
 
 namespace pbf {
 
-int g1_mul_xyzz_run(const G1Work& w, const uint64_t* d_points, const uint64_t* d_scalars, uint64_t n, hipStream_t s) {
+int g1_mul_xyzz_run(const G1Work& w, const uint64_t* d_points, const uint64_t* d_scalars, uint64_t n, uint64_t batch,
+                    hipStream_t s) {
   uint32_t log_n = 0;
   while (((uint64_t)1 << log_n) < n) ++log_n;
-  for (uint64_t i0 = 0; i0 < n; i0 += w.stride) {
-    const uint64_t cnt = std::min(w.stride, n - i0);
+  const uint64_t total = batch * n;
+  for (uint64_t i0 = 0; i0 < total; i0 += w.stride) {
+    const uint64_t cnt = std::min(w.stride, total - i0);
     hipLaunchKernelGGL(k_g1_mul_x, dim3(blocks_of(cnt, GN_T)), dim3(GN_T), 0, s, d_points, d_scalars, w.x, w.tbl,
                        w.stride, i0, cnt, n, log_n);
   }

@@ -36,13 +36,21 @@ int fk20_setup_args(pbf_ctx* ctx, const uint64_t* srs, size_t srs_m, const uint6
   if (srs_m + 1 < n) return fail(PBF_EINVAL, "SRS too short");
   return 0;
 }
-int fk20_open_args(pbf_ctx* ctx, const uint64_t* xext, size_t n, const uint64_t* omega2, const uint64_t* polys,
-                   size_t len, size_t pitch, size_t batch, const uint64_t* weights, const uint64_t* out_w, U256* w2m) {
-  if (!omega2 || !weights || !out_w) return fail(PBF_EINVAL, "null argument");
+// what the multi-openings check of xext, the domain and the polynomials; the weighted ones add the weights
+int fk20_polys_args(pbf_ctx* ctx, const uint64_t* xext, size_t n, const uint64_t* omega2, const uint64_t* polys,
+                    size_t len, size_t pitch, size_t batch, const uint64_t* out_w, U256* w2m) {
+  if (!omega2 || !out_w) return fail(PBF_EINVAL, "null argument");
   int rc = poly_args(ctx, xext, 0, polys, len, pitch, batch, 0);
   if (rc) return rc;
   if ((rc = fk20_domain(n, omega2, w2m))) return rc;
   if (len > n) return fail(PBF_EINVAL, "len exceeds n");
+  return 0;
+}
+int fk20_open_args(pbf_ctx* ctx, const uint64_t* xext, size_t n, const uint64_t* omega2, const uint64_t* polys,
+                   size_t len, size_t pitch, size_t batch, const uint64_t* weights, const uint64_t* out_w, U256* w2m) {
+  if (!weights) return fail(PBF_EINVAL, "null argument");
+  int rc = fk20_polys_args(ctx, xext, n, omega2, polys, len, pitch, batch, out_w, w2m);
+  if (rc) return rc;
   if (!fr_canonical(weights, batch)) return fail(PBF_EINVAL, "weights must be canonical");
   return 0;
 }
@@ -119,7 +127,16 @@ int open_host(pbf_ctx* ctx, const uint64_t* xext, size_t n, const uint64_t* poly
 // size 2k, a_r[t] = srs[r + l (k-2-t)], b_r[u] = p_(r + l u). xext holds the l
 // transforms of the a_r slab after slab; a call multiplies all 2n points as one vector, sums the
 // l products of every frequency and runs the two transforms at sizes 2k and k.
+//
+// The proofs of each of B polynomials (pbf_kzg_open_cells_each_bn254*) are the
+// same steps with every vector B times as long, and the weighted call is B = 1 of them on the
+// combination c (cells_proofs): the B x 2n products run as ONE vector over the same xext, so a
+// launch is as wide as the tile whatever 2n is and takes polynomials' products together or splits
+// one polynomial's between two launches; their sums, B x 2k, lie behind them; the transforms of
+// sizes 2k and k are the batched G1 NTT (g1_ntt.hip) over B transforms, the size-k ones at the
+// pitch 2k that k_g1_slice leaves them at. Scratch: B x (2n + 2k) points.
 constexpr size_t CELLS_MAX_COUNT = (size_t)1 << 20, CELLS_MAX_VALUES = (size_t)1 << 22;
+constexpr size_t CELLS_EACH_MAX = (size_t)1 << 24;  // batch * n of one call: 4 GiB of products
 constexpr int CV_CH = 32;  // entries per lane of the verifier's sweep
 
 // a[r 2k + t] = srs[r + l (k-2-t)] for t <= k-2 and the identity (0, 0) for k-1 <= t < 2k, r < l
@@ -131,14 +148,18 @@ __global__ void __launch_bounds__(256) k_cells_a(const uint64_t* srs, uint64_t k
   for (int q = 0; q < 8; ++q) a[8 * j + q] = t + 2 <= k ? srs[8 * (r + ((k - 2 - t) << log_l)) + q] : 0;
 }
 
-// b[r k + u] = c_(r + l u), zero from len on: the l inputs of the batched Fr NTT of size 2k
-__global__ void __launch_bounds__(256) k_cells_gather(const uint64_t* c, uint64_t len, uint64_t k, uint32_t log_l,
-                                                      uint64_t* b) {
+// b[p n + r k + u] = scale c_(p, r + l u), zero from len on, polynomial p < total / n at c + 4 p pitch:
+// the l inputs per polynomial of the batched Fr NTT of size 2k (scale: Montgomery form, the
+// inverse transform's (2k)^-1; the product is canonical)
+__global__ void __launch_bounds__(256) k_cells_gather(const uint64_t* c, uint64_t len, uint64_t pitch, uint64_t total,
+                                                      uint64_t k, uint32_t log_l, U256 scale, uint64_t* b) {
   const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= k << log_l) return;
-  const uint64_t src = j / k + ((j % k) << log_l);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) b[4 * j + q] = src < len ? c[4 * src + q] : 0;
+  if (j >= total) return;
+  const uint64_t n = k << log_l, m = j & (n - 1);
+  const uint64_t src = m / k + ((m % k) << log_l);
+  U256 v = u256_zero();
+  if (src < len) v = Fr::mul(scale, u256_from_u64(c + 4 * ((j - m) / n * pitch + src)));
+  u256_to_u64(v, b + 4 * j);
 }
 
 // out[(b k + i) l + t] = y[b n + i + k t]: the values of a transform of size n = k l, cell-major
@@ -155,12 +176,17 @@ __global__ void __launch_bounds__(256) k_cells_ystore(const uint64_t* y, uint64_
 // chat_i = sum_{r<l} prod_(r 2k + i) for i < 2k, one lane per frequency. k_g1_mul_x left product
 // j of the 2n at x[bitrev_2n((2n - j) mod 2n)]; the sum goes to out[bitrev_2k((2k - i) mod 2k)],
 // where the stages of size 2k read the input of an inverse transform. add2 is the complete
-// addition: equal, opposite and identity operands are ordinary inputs.
-__global__ void __launch_bounds__(GN_T) __attribute__((amdgpu_waves_per_eu(2))) k_cells_sum(const Xyzz* x, Xyzz* out, uint32_t log_k2,
+// addition: equal, opposite and identity operands are ordinary inputs. Lane t < total = batch x 2k
+// is frequency i = t mod 2k of polynomial t / 2k, whose products lie at x + 2n (t / 2k) and whose
+// sums go to out + 2k (t / 2k).
+__global__ void __launch_bounds__(GN_T) __attribute__((amdgpu_waves_per_eu(2))) k_cells_sum(const Xyzz* x, Xyzz* out, uint64_t total, uint32_t log_k2,
                                                    uint32_t log_l) {
-  const uint64_t i = (uint64_t)blockIdx.x * GN_T + threadIdx.x;
+  const uint64_t t = (uint64_t)blockIdx.x * GN_T + threadIdx.x;
   const uint64_t k2 = (uint64_t)1 << log_k2, n2 = k2 << log_l;
-  if (i >= k2) return;
+  if (t >= total) return;
+  const uint64_t i = t & (k2 - 1);
+  x += (t - i) << log_l;
+  out += t - i;
   const uint32_t log_n2 = log_k2 + log_l;
   Xyzz acc = ld_pt(x + (__brevll((n2 - i) & (n2 - 1)) >> (64 - log_n2)));
 #pragma unroll 1
@@ -228,6 +254,68 @@ int cells_open_args(pbf_ctx* ctx, const uint64_t* xext, size_t n, size_t l, cons
   if (rc) return rc;
   return kzg_l_check(n, l, log_l);
 }
+int cells_each_args(pbf_ctx* ctx, const uint64_t* xext, size_t n, size_t l, const uint64_t* omega2,
+                    const uint64_t* polys, size_t len, size_t pitch, size_t batch, const uint64_t* out_w, U256* w2m,
+                    uint32_t* log_l) {
+  int rc = fk20_polys_args(ctx, xext, n, omega2, polys, len, pitch, batch, out_w, w2m);
+  if (rc || (rc = kzg_l_check(n, l, log_l))) return rc;
+  if (batch > CELLS_EACH_MAX / n) return fail(PBF_EINVAL, "this version supports batch * n <= 2^24");
+  return 0;
+}
+
+// out_y of both cell openings: the values of every polynomial, stored cell-major (l = 1 and l = n:
+// as the transform leaves them); wm = omega, of order n
+int cells_values(pbf_ctx* ctx, const U256& wm, const uint64_t* d_polys, size_t len, size_t pitch, size_t batch,
+                 size_t n, size_t l, uint32_t log_l, uint64_t* d_out_y, hipStream_t s) {
+  uint64_t om[4];
+  hout(om, wm);
+  const bool direct = l == 1 || l == n;
+  DevBuf& by = ctx->buf("kzg.cells.y");
+  int rc;
+  if (!direct && (rc = by.ensure(batch * n * 32))) return rc;
+  uint64_t* y = direct ? d_out_y : (uint64_t*)by.p;
+  if ((rc = polys_ntt(ctx, om, d_polys, len, pitch, batch, n, y, s))) return rc;
+  return direct ? 0 : cells_ystore_run(y, batch, n / l, log_l, d_out_y, s);
+}
+
+// d_out_w[p k + i] = W_i of polynomial p < np (len > l coefficients at d_polys + 4 p pitch): the
+// steps of the section's head, every vector np times as long. The weighted call is np = 1 on c.
+int cells_proofs(pbf_ctx* ctx, const uint64_t* d_xext, size_t n, size_t l, uint32_t log_l, const U256& w2m,
+                 const uint64_t* d_polys, size_t len, size_t pitch, size_t np, uint64_t* d_out_w, hipStream_t s) {
+  const uint64_t one[4] = {1, 0, 0, 0};
+  const uint64_t k = n / l, k2 = 2 * k, n2 = 2 * (uint64_t)n;
+  DevBuf &bg = ctx->buf("kzg.cells.b"), &bb = ctx->buf("kzg.fk20.bhat");
+  G1Work w;
+  int rc;
+  if ((rc = bg.ensure(np * n * 32)) || (rc = bb.ensure(np * n2 * 32)) ||
+      (rc = g1_work(ctx, np * (l == 1 ? n2 : n2 + k2), np * n2, &w)))
+    return rc;
+  uint64_t *b = (uint64_t*)bg.p, *bhat = (uint64_t*)bb.p;
+  // b_(p,r) = (2k)^-1 times every l-th coefficient of p: the inverse transform's factor rides on them
+  hipLaunchKernelGGL(k_cells_gather, dim3((uint32_t)((np * n + 255) / 256)), dim3(256), 0, s, d_polys, (uint64_t)len,
+                     (uint64_t)pitch, (uint64_t)(np * n), k, log_l, fr_inv(hm64(k2)), b);
+  PBF_HIP(hipGetLastError());
+  const U256 wlm = fr_pow(w2m, l);  // omega2^l, of order 2k; its square omega^l, of order k
+  uint64_t wl[4];
+  hout(wl, wlm);
+  if ((rc = pbf_ntt_fr256_coset_batch_dev(ctx, wl, one, b, k, bhat, k2, np * l, 0, s))) return rc;
+  // the np x 2n products as one vector; with l = 1 they lie where the inverse transforms read
+  // them, else their sums per frequency are put there, behind the products
+  if ((rc = g1_mul_xyzz_run(w, d_xext, bhat, n2, np, s))) return rc;
+  if (l > 1) {
+    uint32_t log_k2 = 0;
+    while (((uint64_t)1 << log_k2) < k2) ++log_k2;
+    hipLaunchKernelGGL(k_cells_sum, dim3((uint32_t)((np * k2 + GN_T - 1) / GN_T)), dim3(GN_T), 0, s, (const Xyzz*)w.x,
+                       w.x + np * n2, (uint64_t)(np * k2), log_k2, log_l);
+    PBF_HIP(hipGetLastError());
+    w.x += np * n2;
+  }
+  // c = a * b summed over the slabs; h = c[k-1 .. 2k-1); W = NTT_k(h), at the pitch 2k throughout
+  if ((rc = g1_ntt_stages(ctx, wlm, k2, np, k2, w, s)) || (rc = g1_ntt_slice(w, k, np, s)) ||
+      (rc = g1_ntt_stages(ctx, Fr::mul(wlm, wlm), k, np, k2, w, s)))
+    return rc;
+  return g1_ntt_store(w, d_out_w, k, np, k2, s);
+}
 
 }  // namespace
 
@@ -252,7 +340,7 @@ extern "C" int pbf_kzg_fk20_setup_bn254_dev(pbf_ctx* ctx, const uint64_t* d_srs,
   }
   hipLaunchKernelGGL(k_fk20_a, dim3((uint32_t)((2 * n + 255) / 256)), dim3(256), 0, s, d_srs, (uint64_t)n, d_xext);
   PBF_HIP(hipGetLastError());
-  return g1_ntt_run(ctx, w2m, d_xext, d_xext, 2 * n, 0, s);
+  return g1_ntt_run(ctx, w2m, d_xext, d_xext, 2 * n, 1, 0, s);
 }
 
 extern "C" int pbf_kzg_fk20_setup_bn254(pbf_ctx* ctx, const uint64_t* srs, size_t srs_m, const uint64_t* omega2,
@@ -293,10 +381,10 @@ extern "C" int pbf_kzg_open_all_bn254_dev(pbf_ctx* ctx, const uint64_t* d_xext, 
     return rc;
   if ((rc = pbf_ntt_fr256_coset_batch_dev(ctx, omega2, one, comb, len, bhat, n2, 1, 0, s))) return rc;
   // chat_i = [bhat_i] xext_i where the inverse transform reads it; c = a * b; h = c[n-1 .. 2n-1); W = NTT_n(h)
-  if ((rc = g1_mul_xyzz_run(w, d_xext, bhat, n2, s)) || (rc = g1_ntt_stages(ctx, w2m, n2, w, s)) ||
-      (rc = g1_ntt_slice(w, n, s)) || (rc = g1_ntt_stages(ctx, wm, n, w, s)))
+  if ((rc = g1_mul_xyzz_run(w, d_xext, bhat, n2, 1, s)) || (rc = g1_ntt_stages(ctx, w2m, n2, 1, n2, w, s)) ||
+      (rc = g1_ntt_slice(w, n, 1, s)) || (rc = g1_ntt_stages(ctx, wm, n, 1, n2, w, s)))
     return rc;
-  return g1_ntt_store(w, d_out_w, n, s);
+  return g1_ntt_store(w, d_out_w, n, 1, n2, s);
 }
 
 extern "C" int pbf_kzg_open_all_bn254(pbf_ctx* ctx, const uint64_t* xext, size_t n, const uint64_t* omega2,
@@ -320,17 +408,15 @@ extern "C" int pbf_kzg_cells_setup_bn254_dev(pbf_ctx* ctx, const uint64_t* d_srs
   if (rc) return rc;
   PBF_HIP(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
-  const uint64_t k = n / l, k2 = 2 * k;
+  const uint64_t k = n / l;
   if (k == 1) {  // every a_r is two identities, and so is its transform
     PBF_HIP(hipMemsetAsync(d_xext, 0, 2 * n * 64, s));
     return PBF_OK;
   }
   hipLaunchKernelGGL(k_cells_a, dim3((uint32_t)((2 * n + 255) / 256)), dim3(256), 0, s, d_srs, k, log_l, d_xext);
   PBF_HIP(hipGetLastError());
-  const U256 wlm = fr_pow(w2m, l);  // omega2^l, of order 2k
-  for (uint64_t r = 0; r < l; ++r)
-    if ((rc = g1_ntt_run(ctx, wlm, d_xext + 8 * r * k2, d_xext + 8 * r * k2, k2, 0, s))) return rc;
-  return PBF_OK;
+  // the l slabs are one batch of transforms of size 2k, root omega2^l, in place
+  return g1_ntt_run(ctx, fr_pow(w2m, l), d_xext, d_xext, 2 * k, l, 0, s);
 }
 
 extern "C" int pbf_kzg_cells_setup_bn254(pbf_ctx* ctx, const uint64_t* srs, size_t srs_m, const uint64_t* omega2,
@@ -355,55 +441,55 @@ extern "C" int pbf_kzg_open_cells_bn254_dev(pbf_ctx* ctx, const uint64_t* d_xext
   if (rc) return rc;
   PBF_HIP(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
-  const uint64_t one[4] = {1, 0, 0, 0};
-  const uint64_t k = n / l, k2 = 2 * k, n2 = 2 * (uint64_t)n;
-  const U256 wm = Fr::mul(w2m, w2m);  // omega = omega2^2, of order n
-  uint64_t om[4];
-  hout(om, wm);
-  if (d_out_y) {  // the values of every polynomial, stored cell-major (l = 1 and l = n: as the transform leaves them)
-    const bool direct = l == 1 || k == 1;
-    DevBuf& by = ctx->buf("kzg.cells.y");
-    if (!direct && (rc = by.ensure(batch * n * 32))) return rc;
-    uint64_t* y = direct ? d_out_y : (uint64_t*)by.p;
-    if ((rc = polys_ntt(ctx, om, d_polys, len, pitch, batch, n, y, s))) return rc;
-    if (!direct && (rc = cells_ystore_run(y, batch, k, log_l, d_out_y, s))) return rc;
-  }
+  const uint64_t k = n / l;
+  if (d_out_y &&
+      (rc = cells_values(ctx, Fr::mul(w2m, w2m), d_polys, len, pitch, batch, n, l, log_l, d_out_y, s)))  // omega = omega2^2
+    return rc;
   if (len <= l) {  // degree below l: every quotient is zero, every W the identity (k = 1 included)
     PBF_HIP(hipMemsetAsync(d_out_w, 0, k * 64, s));
     return PBF_OK;
   }
-  DevBuf &bc = ctx->buf("kzg.comb"), &bg = ctx->buf("kzg.cells.b"), &bb = ctx->buf("kzg.fk20.bhat");
-  G1Work w;
-  if ((rc = bc.ensure(len * 32)) || (rc = bg.ensure(n * 32)) || (rc = bb.ensure(n2 * 32)) ||
-      (rc = g1_work(ctx, l == 1 ? n2 : n2 + k2, n2, &w)))
+  DevBuf& bc = ctx->buf("kzg.comb");
+  if ((rc = bc.ensure(len * 32))) return rc;
+  uint64_t* comb = (uint64_t*)bc.p;
+  // c = sum_b w_b p_b, then its proofs
+  if ((rc = kzg_comb(d_polys, len, pitch, batch, scaled_weights(weights, batch, fr_one_m()).data(), comb, s)))
     return rc;
-  uint64_t *comb = (uint64_t*)bc.p, *b = (uint64_t*)bg.p, *bhat = (uint64_t*)bb.p;
-  // c = (2k)^-1 sum_b w_b p_b
-  if ((rc = kzg_comb(d_polys, len, pitch, batch, scaled_weights(weights, batch, fr_inv(hm64(k2))).data(), comb, s)))
+  return cells_proofs(ctx, d_xext, n, l, log_l, w2m, comb, len, len, 1, d_out_w, s);
+}
+
+extern "C" int pbf_kzg_open_cells_each_bn254_dev(pbf_ctx* ctx, const uint64_t* d_xext, size_t n, size_t l,
+                                                 const uint64_t* omega2, const uint64_t* d_polys, size_t len,
+                                                 size_t pitch, size_t batch, uint64_t* d_out_y, uint64_t* d_out_w,
+                                                 void* stream) {
+  U256 w2m;
+  uint32_t log_l;
+  int rc = cells_each_args(ctx, d_xext, n, l, omega2, d_polys, len, pitch, batch, d_out_w, &w2m, &log_l);
+  if (rc) return rc;
+  PBF_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (d_out_y &&
+      (rc = cells_values(ctx, Fr::mul(w2m, w2m), d_polys, len, pitch, batch, n, l, log_l, d_out_y, s)))  // omega = omega2^2
     return rc;
-  hipLaunchKernelGGL(k_cells_gather, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, (const uint64_t*)comb,
-                     (uint64_t)len, k, log_l, b);
-  PBF_HIP(hipGetLastError());
-  const U256 wlm = fr_pow(w2m, l);  // omega2^l, of order 2k; its square omega^l, of order k
-  uint64_t wl[4];
-  hout(wl, wlm);
-  if ((rc = pbf_ntt_fr256_coset_batch_dev(ctx, wl, one, b, k, bhat, k2, l, 0, s))) return rc;
-  // the 2n products as one vector; with l = 1 they lie where the inverse transform reads them,
-  // else their sums per frequency are put there, behind the products
-  if ((rc = g1_mul_xyzz_run(w, d_xext, bhat, n2, s))) return rc;
-  if (l > 1) {
-    uint32_t log_k2 = 0;
-    while (((uint64_t)1 << log_k2) < k2) ++log_k2;
-    hipLaunchKernelGGL(k_cells_sum, dim3((uint32_t)((k2 + GN_T - 1) / GN_T)), dim3(GN_T), 0, s, (const Xyzz*)w.x,
-                       w.x + n2, log_k2, log_l);
-    PBF_HIP(hipGetLastError());
-    w.x += n2;
+  if (len <= l) {  // degree below l: every quotient is zero, every W the identity (k = 1 included)
+    PBF_HIP(hipMemsetAsync(d_out_w, 0, batch * (n / l) * 64, s));
+    return PBF_OK;
   }
-  // c = a * b summed over the slabs; h = c[k-1 .. 2k-1); W = NTT_k(h)
-  if ((rc = g1_ntt_stages(ctx, wlm, k2, w, s)) || (rc = g1_ntt_slice(w, k, s)) ||
-      (rc = g1_ntt_stages(ctx, Fr::mul(wlm, wlm), k, w, s)))
-    return rc;
-  return g1_ntt_store(w, d_out_w, k, s);
+  return cells_proofs(ctx, d_xext, n, l, log_l, w2m, d_polys, len, pitch, batch, d_out_w, s);
+}
+
+extern "C" int pbf_kzg_open_cells_each_bn254(pbf_ctx* ctx, const uint64_t* xext, size_t n, size_t l,
+                                             const uint64_t* omega2, const uint64_t* polys, size_t len, size_t pitch,
+                                             size_t batch, uint64_t* out_y, uint64_t* out_w) {
+  U256 w2m;
+  uint32_t log_l;
+  int rc = cells_each_args(ctx, xext, n, l, omega2, polys, len, pitch, batch, out_w, &w2m, &log_l);
+  if (rc) return rc;
+  return open_host(ctx, xext, n, polys, len, pitch, batch, out_y, out_w, batch * (n / l),
+                   [&](const uint64_t* d_xext, const uint64_t* d_polys, uint64_t* d_y, uint64_t* d_w, hipStream_t s) {
+                     return pbf_kzg_open_cells_each_bn254_dev(ctx, d_xext, n, l, omega2, d_polys, len, len, batch, d_y, d_w,
+                                                              s);
+                   });
 }
 
 extern "C" int pbf_kzg_open_cells_bn254(pbf_ctx* ctx, const uint64_t* xext, size_t n, size_t l, const uint64_t* omega2,

@@ -86,22 +86,29 @@ struct G1Work {
 int g1_work(pbf_ctx* ctx, uint64_t points, uint64_t products, G1Work* w);
 // *bad = some of the n device points (8 x u64) is not canonical or not on the curve; synchronises s
 int g1_check_run(pbf_ctx* ctx, const uint64_t* d_pts, uint64_t n, hipStream_t s, int* bad);
+// All of these take `batch` transforms of one size n and omega, transform q at w.x + q pitch
+// (pitch >= n points); one launch carries butterflies of several transforms.
 // The log2 n butterfly stages over w.x[0 .. n), n >= 2: input at bit-reversed indices, output in
 // natural order, unscaled: x[k] = sum_j [omega^(jk)] in[j]. With in[j] stored at the bit-reversed
 // index of (n - j) mod n it is the inverse transform without its factor n^-1.
-int g1_ntt_stages(pbf_ctx* ctx, const U256& wm, uint64_t n, const G1Work& w, hipStream_t s);
+// w from g1_work(ctx, ., batch n/2 or more, .).
+int g1_ntt_stages(pbf_ctx* ctx, const U256& wm, uint64_t n, uint64_t batch, uint64_t pitch, const G1Work& w,
+                  hipStream_t s);
 // w.x[0 .. 2n) in natural order -> its entries n - 1 .. 2n - 2 and the identity, as the input of
-// the stages of size n, in w.x[0 .. n) (n >= 2)
-int g1_ntt_slice(const G1Work& w, uint64_t n, hipStream_t s);
-// d_out[i] = w.x[i] as canonical affine, i < n
-int g1_ntt_store(const G1Work& w, uint64_t* d_out, uint64_t n, hipStream_t s);
-// pbf_ntt_g1_bn254_dev past its argument checks (wm: omega of order n, Montgomery form)
-int g1_ntt_run(pbf_ctx* ctx, const U256& wm, const uint64_t* d_in, uint64_t* d_out, uint64_t n, int inverse,
-               hipStream_t s);
-// g1_mul.hip: w.x[bitrev((n - i) mod n)] = [k_i]P_i for i < n (n >= 2 a power of two): n canonical
-// affine points times n canonical scalars, left as Xyzz where g1_ntt_stages reads the input of an
-// inverse transform. w from g1_work(ctx, n, n, .).
-int g1_mul_xyzz_run(const G1Work& w, const uint64_t* d_points, const uint64_t* d_scalars, uint64_t n, hipStream_t s);
+// the stages of size n, in w.x[0 .. n) (n >= 2). Transform q at w.x + 2 q n before and after: the
+// transforms of size n keep the pitch 2n.
+int g1_ntt_slice(const G1Work& w, uint64_t n, uint64_t batch, hipStream_t s);
+// d_out[q n + i] = (w.x + q pitch)[i] as canonical affine, i < n: d_out is compact
+int g1_ntt_store(const G1Work& w, uint64_t* d_out, uint64_t n, uint64_t batch, uint64_t pitch, hipStream_t s);
+// pbf_ntt_g1_bn254_batch_dev past its argument checks (wm: omega of order n, Montgomery form)
+int g1_ntt_run(pbf_ctx* ctx, const U256& wm, const uint64_t* d_in, uint64_t* d_out, uint64_t n, uint64_t batch,
+               int inverse, hipStream_t s);
+// g1_mul.hip: (w.x + q n)[bitrev((n - i) mod n)] = [k_(q n + i)]P_i for i < n, q < batch (n >= 2 a
+// power of two): the same n canonical affine points times batch x n canonical scalars, left as Xyzz
+// where g1_ntt_stages (pitch n) reads the inputs of inverse transforms. The batch x n products are
+// one vector: a launch is as wide as the tile whatever n. w from g1_work(ctx, ., batch n, .).
+int g1_mul_xyzz_run(const G1Work& w, const uint64_t* d_points, const uint64_t* d_scalars, uint64_t n, uint64_t batch,
+                    hipStream_t s);
 
 // verify.hip: Plonk::verify's preprocessing, shared by the single and the batched verifier:
 // pre = the commitments of q_m q_l q_r q_o q_c s_sigma_1..3 (canonical affine), from the

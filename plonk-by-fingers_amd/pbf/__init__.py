@@ -127,6 +127,8 @@ SIGNATURES = [
                                             ctypes.POINTER(ctypes.c_int)]),
     ("pbf_ntt_g1_bn254", ctypes.c_int, [_vp, _p64, _p64, _p64, _sz, ctypes.c_int]),
     ("pbf_ntt_g1_bn254_dev", ctypes.c_int, [_vp, _p64, _vp, _vp, _sz, ctypes.c_int, _vp]),
+    ("pbf_ntt_g1_bn254_batch", ctypes.c_int, [_vp, _p64, _p64, _p64, _sz, _sz, ctypes.c_int]),
+    ("pbf_ntt_g1_bn254_batch_dev", ctypes.c_int, [_vp, _p64, _vp, _vp, _sz, _sz, ctypes.c_int, _vp]),
     ("pbf_kzg_open_evals_bn254", ctypes.c_int, [_vp, _p64, _sz, _p64, _p64, _sz, _sz, _p64, _p64, _p64, _p64]),
     ("pbf_kzg_open_evals_bn254_dev", ctypes.c_int, [_vp, _vp, _sz, _p64, _vp, _sz, _sz, _p64, _p64, _p64, _p64,
                                                     _vp]),
@@ -141,7 +143,9 @@ SIGNATURES = [
     ("pbf_kzg_open_cells_bn254", ctypes.c_int, [_vp, _p64, _sz, _sz, _p64, _p64, _sz, _sz, _sz, _p64, _p64, _p64]),
     ("pbf_kzg_open_cells_bn254_dev", ctypes.c_int, [_vp, _vp, _sz, _sz, _p64, _vp, _sz, _sz, _sz, _p64, _vp, _vp,
                                                     _vp]),
-    ("pbf_kzg_verify_cells_bn254", ctypes.c_int, [_vp, _p64, _p64, _sz, _p64, _sz, _sz, _sz, _p64, _p64, _p64, _p64,
+    ("pbf_kzg_open_cells_each_bn254", ctypes.c_int, [_vp, _p64, _sz, _sz, _p64, _p64, _sz, _sz, _sz, _p64, _p64]),
+    ("pbf_kzg_open_cells_each_bn254_dev", ctypes.c_int, [_vp, _vp, _sz, _sz, _p64, _vp, _sz, _sz, _sz, _vp, _vp, _vp]),
+    ("pbf_kzg_verify_cells_bn254",ctypes.c_int, [_vp, _p64, _p64, _sz, _p64, _sz, _sz, _sz, _p64, _p64, _p64, _p64,
                                                   _p64, ctypes.POINTER(ctypes.c_int)]),
     ("pbf_kzg_recover_cells_bn254", ctypes.c_int, [_vp, _p64, _sz, _sz, _sz, _sz, _p64, _p64, _sz, _p64, _sz, _p64,
                                                    ctypes.POINTER(ctypes.c_int)]),
@@ -614,6 +618,24 @@ class Context:
         _check(self.lib.pbf_ntt_g1_bn254_dev(self.h, _ptr(ints_to_limbs([omega])), _vp(d_in), _vp(d_out), n,
                                              int(inverse), _vp(stream) if stream else None))
 
+    def ntt_g1_batch(self, omega: int, points, n: int, inverse: bool = False) -> list:
+        """pbf_ntt_g1_bn254_batch: len(points) / n transforms of size n under one omega, transform b
+        the points[b*n:(b+1)*n]; each is what ntt_g1 returns for that slice. Every point is checked."""
+        batch = len(points) // n if n else 0
+        if not n or batch * n != len(points):
+            raise ValueError("points must hold whole transforms of size n")
+        out = np.zeros(8 * max(len(points), 1), dtype=np.uint64)
+        _check(self.lib.pbf_ntt_g1_bn254_batch(self.h, _ptr(ints_to_limbs([omega])), _ptr(_g1_limbs(points)),
+                                               _ptr(out), n, batch, int(inverse)))
+        return self._points(out)[:len(points)]
+
+    def ntt_g1_batch_dev(self, omega: int, d_in: int, d_out: int, n: int, batch: int, inverse: bool = False,
+                         stream: int = 0) -> None:
+        """The same on batch x n device points (compact, unchecked), enqueued on stream; d_in may be
+        d_out."""
+        _check(self.lib.pbf_ntt_g1_bn254_batch_dev(self.h, _ptr(ints_to_limbs([omega])), _vp(d_in), _vp(d_out), n,
+                                                   batch, int(inverse), _vp(stream) if stream else None))
+
     def srs_lagrange(self, srs, n: int, omega: int | None = None) -> list:
         """The Lagrange-basis SRS [L_i(s)]G, i < n, of srs = [s^j G]: the inverse G1 NTT of its
         first n points (no trapdoor). omega defaults to the library's root of unity of order n."""
@@ -735,6 +757,32 @@ class Context:
                                                      _ptr(ints_to_limbs(list(weights))),
                                                      _vp(d_out_y) if d_out_y else None, _vp(d_out_w),
                                                      _vp(stream) if stream else None))
+
+    def kzg_open_cells_each(self, xext, l: int, omega2: int, polys, pitch: int | None = None, with_y: bool = True):
+        """pbf_kzg_open_cells_each_bn254: the cell proofs of every polynomial in one call:
+        (ys or None, ws) with ws[b] the k proofs kzg_open_cells gives for polynomial b alone under
+        weight 1, and ys as kzg_open_cells returns it."""
+        a, ln, pitch, batch = self._poly_limbs(polys, pitch)
+        n = len(xext) // 2
+        k = n // l if l else 0
+        ys = np.zeros(4 * max(batch * n, 1), dtype=np.uint64)
+        w = np.zeros(8 * max(batch * k, 1), dtype=np.uint64)
+        _check(self.lib.pbf_kzg_open_cells_each_bn254(self.h, _ptr(_g1_limbs(xext)), n, l,
+                                                      _ptr(ints_to_limbs([omega2])), _ptr(a), ln, pitch, batch,
+                                                      _ptr(ys) if with_y else None, _ptr(w)))
+        v = limbs_to_ints(ys)
+        cells = [[v[(b * k + i) * l:(b * k + i + 1) * l] for i in range(k)] for b in range(batch)]
+        pts = self._points(w)
+        return (cells if with_y else None), [pts[b * k:(b + 1) * k] for b in range(batch)]
+
+    def kzg_open_cells_each_dev(self, d_xext: int, n: int, l: int, omega2: int, d_polys: int, length: int, pitch: int,
+                                batch: int, d_out_y: int, d_out_w: int, stream: int = 0) -> None:
+        """The same on the device: d_out_y (batch x n values, cell-major, or 0 for none) and d_out_w
+        (batch x n / l points, polynomial-major) are written on stream and stay there."""
+        _check(self.lib.pbf_kzg_open_cells_each_bn254_dev(self.h, _vp(d_xext), n, l, _ptr(ints_to_limbs([omega2])),
+                                                          _vp(d_polys), length, pitch, batch,
+                                                          _vp(d_out_y) if d_out_y else None, _vp(d_out_w),
+                                                          _vp(stream) if stream else None))
 
     def kzg_verify_cells(self, g2s, srs, omega: int, n: int, l: int, entries, rhos) -> bool:
         """pbf_kzg_verify_cells_bn254: g2s = [G2, [s^l]G2]; srs the first l points (or more);
