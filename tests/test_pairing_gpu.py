@@ -123,9 +123,46 @@ def test_lane_engine_two_wave_build_matches(lane_ctx):
 
 def test_g2_mul_matches_oracle(ctx):
     rng = random.Random(9)
-    ks = [0, 1, 2, B.R - 1, rng.randrange(B.R), rng.randrange(B.R)]
+    ks = [0, 1, 2, B.R - 1, rng.randrange(B.R), rng.randrange(B.R)] + G2_EXIT_SCALARS
     got = ctx.g2_bn254_mul([B.G2_GEN] * len(ks), ks)
-    assert got == [B.g2_mul(B.G2_GEN, k) for k in ks]
+    assert got == [B.g2_mul(B.G2_GEN, k) for k in ks]  # the oracle reduces k mod r, the kernel does not
+    assert got[6] is None and got[7] == B.G2_GEN
+    # the identity as the base point, with nonzero scalars
+    assert ctx.g2_bn254_mul([None] * 3, [1, B.R - 1, (1 << 256) - 1]) == [None] * 3
+
+
+# Context.g2_bn254_mul passes any 256-bit scalar on unreduced, and only scalars at or above r enter
+# the two special exits of g2_mul_kernel's affine addition
+G2_EXIT_SCALARS = [
+    B.R,               # the last set bit (253) adds 2^253 P to (r - 2^253) P = -2^253 P: the P + (-P) exit; the identity
+    B.R + 1,           # on from there: the sum passes r without meeting the identity on the way and gives P
+    (1 << 255) - B.R,  # at bit 254 the bits below sum to 2^254 - r = 2^254 P, the base itself: the doubling exit in add
+    (1 << 256) - 1,    # all 256 bits set: an addition at every step, the top bit of the top word included
+]
+
+
+def test_g2_mul_exits_in_one_wave(ctx):
+    """One batch of 70 (a full wave and a ragged one): the scalars that enter the P + (-P) and the
+    doubling exit, identity base points and zero scalars, with ordinary scalars and other base
+    points between them, so that lanes of one wave take different exits at the same step."""
+    rng = random.Random(0x62)
+    bases = [B.G2_GEN, B.g2_mul(B.G2_GEN, 7), B.g2_mul(B.G2_GEN, rng.randrange(1, B.R))]
+    pts, ks = [], []
+    for i in range(70):
+        pts.append(bases[i % 3])
+        ks.append(rng.randrange(1, B.R))
+    for j, lane in enumerate((3, 10, 17, 24, 31, 38, 45, 52, 59, 63, 65, 69)):
+        ks[lane] = G2_EXIT_SCALARS[j % 4]
+    for lane in (5, 33, 66):
+        pts[lane] = None
+    ks[33] = B.R
+    ks[12] = 0
+    assert len(ks) == 70 and all(sum(k == s for k in ks) >= 3 for s in G2_EXIT_SCALARS)
+    assert all(ks[i] not in G2_EXIT_SCALARS or ks[i + 1] not in G2_EXIT_SCALARS for i in range(69))
+    got = ctx.g2_bn254_mul(pts, ks)
+    want = [B.g2_mul(p, k) for p, k in zip(pts, ks)]
+    assert got == want
+    assert all(got[i] is None for i in range(70) if ks[i] == B.R or pts[i] is None or ks[i] == 0)
 
 
 def test_kzg_opening_check(ctx):
