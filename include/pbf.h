@@ -352,6 +352,67 @@ int pbf_plonk_verify_bn254_batch_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q
                                      const uint64_t* u, const uint64_t* rho, const uint64_t* k1k2, int mode, int* ok,
                                      int* ok_each, void* stream);
 
+/* Public inputs: one circuit, many statements. Public input i < npub <= n sits on gate row i:
+ * with PI(w^i) = -pub_i for i < npub, 0 on the other rows of H, and PI(x) its interpolation
+ * (degree < n), the gate equation is
+ *     q_l a + q_r b + q_o c + q_m a b + q_c + PI = 0   on H,
+ * whatever the row's selectors are (the classic public row is q_l = 1, a_i = pub_i). PI(x) enters
+ * the quotient's gate term t_1 (plonk.rs:339-344) and the verifier's step 7 only,
+ *     t_z = (r_z + PI(z) - perm - L_1(z) alpha^2) / Z_H(z),
+ *     PI(z) = -(z^n - 1)/n * sum_{i<npub} pub_i w^i / (z - w^i);
+ * r(x) keeps q_c(x) and gains no PI term in either mode, so r_z and the opening batching are as
+ * without public inputs and the t parts and W_z are those of the new t(x).
+ *   pub: npub x 4 u64, canonical. Prover: a device pointer in the _dev form (like d_abc), a host
+ *   pointer in the host form. Verifiers: a host pointer in both forms (as the proof is); the batch
+ *   takes count x npub x 4, proof-major and compact, one npub per batch (it is a property of the
+ *   circuit). Every other argument, the stream contract, the keys and the options are those of the
+ *   entry point without _pi.
+ * Contract:
+ *   - npub = 0 (pub may then be NULL) is the entry point without _pi: the same launches, bit for
+ *     bit the same output.
+ *   - npub > n, a pub value >= r, or NULL pub with npub > 0 give PBF_EINVAL before anything is
+ *     enqueued, in prover and verifiers alike (pbf_plonk_prove_bn254_pi_dev, whose pub is on the
+ *     device, finds a value >= r in its first kernel, the constraint check, before any other
+ *     work). Public inputs are the caller's statement, not part of a proof, so they are never a
+ *     reason for ok = 0.
+ *   - a witness that does not meet the gate equation including -pub_i gives the "constraints not
+ *     satisfied" PBF_EINVAL (the pre-check keeps the reference's form, its q_l * b term included).
+ *   - the proving and verification keys do not depend on pub: changing pub between calls rebuilds
+ *     nothing. The prover forms q_c(x) + PI(x) on the coset in per-proof scratch it already owns
+ *     (one INTT of n and one coset NTT of 4n per proof; no added buffer); the key's q_c slot is
+ *     never written, and a _pi call does not alter what a later plain call returns on the context.
+ *   - Soundness: the library derives no challenge (as with rho below), so the caller's transcript
+ *     must absorb pub before beta.
+ *   - the sharded and _multi provers take no public inputs.                                      */
+int pbf_plonk_prove_bn254_pi(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies, const uint64_t* abc,
+                             const uint64_t* pub, size_t npub, const uint64_t* chal, const uint64_t* rnd,
+                             const uint64_t* k1k2, const uint64_t* srs, size_t srs_m, int mode, uint64_t* out_pts,
+                             uint64_t* out_f);
+int pbf_plonk_prove_bn254_pi_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
+                                 const uint64_t* d_abc, const uint64_t* d_pub, size_t npub, const uint64_t* chal,
+                                 const uint64_t* rnd, const uint64_t* k1k2, const uint64_t* d_srs, size_t srs_m,
+                                 int mode, uint64_t* out_pts, uint64_t* out_f, void* stream);
+int pbf_plonk_verify_bn254_pi(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies, const uint64_t* srs,
+                              size_t srs_m, const uint64_t* g2, const uint64_t* proof_pts, const uint64_t* proof_f,
+                              const uint64_t* pub, size_t npub, const uint64_t* chal, const uint64_t* u,
+                              const uint64_t* k1k2, int mode, int* ok);
+int pbf_plonk_verify_bn254_pi_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
+                                  const uint64_t* d_srs, size_t srs_m, const uint64_t* g2, const uint64_t* proof_pts,
+                                  const uint64_t* proof_f, const uint64_t* pub, size_t npub, const uint64_t* chal,
+                                  const uint64_t* u, const uint64_t* k1k2, int mode, int* ok, void* stream);
+/* PI_i(z_i) of all `count` proofs comes from one kernel pair (partial fractions per chunk of 256
+ * public inputs and proof, then one fraction per proof), once per call; localisation reuses it. */
+int pbf_plonk_verify_bn254_batch_pi(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies,
+                                    const uint64_t* srs, size_t srs_m, const uint64_t* g2, size_t count,
+                                    const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* pub,
+                                    size_t npub, const uint64_t* chal, const uint64_t* u, const uint64_t* rho,
+                                    const uint64_t* k1k2, int mode, int* ok, int* ok_each);
+int pbf_plonk_verify_bn254_batch_pi_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
+                                        const uint64_t* d_srs, size_t srs_m, const uint64_t* g2, size_t count,
+                                        const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* pub,
+                                        size_t npub, const uint64_t* chal, const uint64_t* u, const uint64_t* rho,
+                                        const uint64_t* k1k2, int mode, int* ok, int* ok_each, void* stream);
+
 /* ---- KZG commitments over BN254 (the scheme inside Plonk::prove / verify, on its own) ------
  * Elements as above: Fr canonical 4 x u64, G1 affine 8 x u64 with (0,0) the identity, G2 16 x u64;
  * srs = [G, sG, s^2 G, ...] as pbf_srs_create_bn254 writes it (G = (1, 2)), g2 = [G2, [s]G2].

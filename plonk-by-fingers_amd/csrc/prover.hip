@@ -174,9 +174,13 @@ __global__ void k_sigma_blk(const uint64_t* copies, const uint64_t* hpow, uint64
   u256_to_u64(h, out + 4 * t);
 }
 
-// Constrains::satisfies (constraints.rs:198-230, with its q_l * b term): gates and copies
+// Constrains::satisfies (constraints.rs:198-230, with its q_l * b term): gates and copies.
+// PI (pbf_plonk_prove_bn254_pi*): rows i < npub check ... + q_c - pub_i = 0; a pub_i >= r sets bad[1]
+// (the _dev form's pub is on the device: this is its canonical check). PI = false is the
+// kernel of the plain entries, which pass pub = null and npub = 0.
+template <bool PI>
 __global__ void k_satisfies(const uint64_t* q, const uint64_t* abc, const uint64_t* copies, uint64_t n, uint64_t row0,
-                            uint64_t rows, int* bad) {
+                            uint64_t rows, const uint64_t* pub, uint64_t npub, int* bad) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= rows) return;
   const uint64_t i = row0 + t;
@@ -190,6 +194,11 @@ __global__ void k_satisfies(const uint64_t* q, const uint64_t* abc, const uint64
   r = Fr::add(r, Fr::mul_tp(qo, c));
   r = Fr::add(r, Fr::mul_tp(Fr::mul_tp(qm, a), b));
   r = Fr::add(r, qc);
+  if (PI && i < npub) {
+    const U256 p = ld(pub + 4 * i);
+    if (Fr::geq_p(p)) atomicOr(bad + 1, 1);  // its own word: the plain stores below do not touch it
+    else r = Fr::sub(r, Fr::from_mont(p));   // lowered to degree -1, as q_c
+  }
   if (!Fr::is_zero(r)) *bad = 1;
   for (int col = 0; col < 3; ++col) {
     const uint64_t kind = copies[2 * (col * n + i)], idx = copies[2 * (col * n + i) + 1];
@@ -384,6 +393,16 @@ __global__ void k_lincomb(LinComb L, uint64_t* out, uint64_t count) {
 __global__ void k_mul(const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t count) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < count) u256_to_u64(Fr::mul_tp(u256_from_u64(a + 4 * i), u256_from_u64(b + 4 * i)), out + 4 * i);
+}
+
+// Public inputs (pbf_plonk_prove_bn254_pi*): u[i] = q_c[i] - pub[i] for i < npub, q_c[i] from there
+// on (i < n), canonical: the values on H of q_c(x) + PI(x), the quotient's per-proof q_c operand
+__global__ void k_qc_minus_pub(const uint64_t* qc, const uint64_t* pub, uint64_t npub, uint64_t* u, uint64_t n) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  U256 v = u256_from_u64(qc + 4 * i);
+  if (i < npub) v = Fr::sub(v, u256_from_u64(pub + 4 * i));
+  u256_to_u64(v, u + 4 * i);
 }
 
 // t(x_i) for x_i = g w_N^i on the coset (N = 4n): the numerator of plonk.rs:358-368
@@ -1319,6 +1338,8 @@ struct ProveState {
   ProverBufs B;  // context-owned scratch (one ctx per host thread, pbf.h)
   int mode = 0;
   const uint64_t *d_q = nullptr, *d_copies = nullptr, *d_abc = nullptr;
+  const uint64_t* d_pub = nullptr;  // public inputs (one GPU; npub = 0: none)
+  uint64_t npub = 0;
   PlonkChallenges ch;
   U256 bl[9];  // the blinders b1..b9
   // proving key: on (option prover.pk), found valid in the context, and the key to store once built
@@ -1444,7 +1465,8 @@ static int prove_sharded(ProveState& S) {
   uint64_t* recv = (uint64_t*)P.comm->recv;
 
   // ---- satisfies (constraints.rs:198-230) on this rank's rows, agreed by every rank
-  hipLaunchKernelGGL(k_satisfies, dim3(blocks_for(Bn)), dim3(256), 0, s, d_q, d_abc, d_copies, n, r * Bn, Bn, P.d_bad);
+  hipLaunchKernelGGL(k_satisfies<false>, dim3(blocks_for(Bn)), dim3(256), 0, s, d_q, d_abc, d_copies, n, r * Bn, Bn,
+                     (const uint64_t*)nullptr, (uint64_t)0, P.d_bad);
   PBF_HIP(hipGetLastError());
   if ((rc = P.agree("constraints not satisfied by the assignment (constraints.rs:198)"))) return rc;
   P.mark("satisfies (rows)");
@@ -1849,10 +1871,24 @@ static int prove_single(ProveState& S) {
   uint64_t* W2 = work + 8 * N;
 
   // ---- satisfies (constraints.rs:198-230)
-  hipLaunchKernelGGL(k_satisfies, dim3(blocks_for(n)), dim3(256), 0, s, d_q, d_abc, d_copies, (uint64_t)n, (uint64_t)0,
-                     (uint64_t)n, P.d_bad);
-  PBF_HIP(hipGetLastError());
-  if ((rc = P.check_bad("constraints not satisfied by the assignment (constraints.rs:198)"))) return rc;
+  const uint64_t* d_pub = S.d_pub;
+  const uint64_t npub = S.npub;  // 0: the plain entries, and every launch below is theirs
+  if (npub) {
+    PBF_HIP(hipMemsetAsync(P.d_bad + 1, 0, sizeof(int), s));
+    hipLaunchKernelGGL(k_satisfies<true>, dim3(blocks_for(n)), dim3(256), 0, s, d_q, d_abc, d_copies, (uint64_t)n,
+                       (uint64_t)0, (uint64_t)n, d_pub, npub, P.d_bad);
+    PBF_HIP(hipGetLastError());
+    int bad[2] = {0, 0};
+    PBF_HIP(hipMemcpyAsync(bad, P.d_bad, sizeof(bad), hipMemcpyDeviceToHost, s));
+    PBF_HIP(hipStreamSynchronize(s));
+    if (bad[1]) return fail(PBF_EINVAL, "public input not canonical");
+    if (bad[0]) return fail(PBF_EINVAL, "constraints not satisfied by the assignment (constraints.rs:198)");
+  } else {
+    hipLaunchKernelGGL(k_satisfies<false>, dim3(blocks_for(n)), dim3(256), 0, s, d_q, d_abc, d_copies, (uint64_t)n,
+                       (uint64_t)0, (uint64_t)n, (const uint64_t*)nullptr, (uint64_t)0, P.d_bad);
+    PBF_HIP(hipGetLastError());
+    if ((rc = P.check_bad("constraints not satisfied by the assignment (constraints.rs:198)"))) return rc;
+  }
   P.mark("satisfies");
 
   // ---- h = w^i, sigma labels (plonk.rs:124, 181-189, 222-224)
@@ -1944,6 +1980,21 @@ static int prove_single(ProveState& S) {
   P.mark(pk_hit ? "round 3 coset NTTs (4, key)" : "round 3 coset NTTs (13)");
   QuotArgs qa;
   if ((rc = quot_args(S, nullptr, qa))) return rc;  // z(w x): z at index i + 4
+  if (npub) {
+    // t_1 gains PI(x) (plonk.rs:339-344 with public inputs): the quotient reads q_c(x) + PI(x) where
+    // it read q_c(x), from a per-proof slot -- the key's q_c slot is left as it is. Its values on H
+    // are q_c[i] - pub[i]; one INTT and one coset NTT make the 4n coset values, raw like the q_c
+    // slot (QUOT_DEG[8]). W1 and W2 are free here: the round's transforms run in the context's NTT
+    // scratch, the quotient writes W0, and r(x) takes W1 only in round 4.
+    hipLaunchKernelGGL(k_qc_minus_pub, dim3(blocks_for(n)), dim3(256), 0, s, d_q + 16 * n, d_pub, npub, W1, (uint64_t)n);
+    PBF_HIP(hipGetLastError());
+    if ((rc = P.ntt(P.w_plain, W1, W1, n, 1, 1))) return rc;
+    const uint64_t* src = W1;
+    const uint64_t len = n;
+    if ((rc = P.coset_ntt_batch(1, &src, &len, &P.g, W2, QUOT_DEG + 8))) return rc;
+    qa.qc = W2;
+    P.mark("round 3 public inputs (INTT + coset NTT)");
+  }
   uint64_t* tq = (uint64_t*)B.t.p;
   launch_quotient(qa, W0, ctx->options.num("ntt256.l29", 1) != 0, s);
   PBF_HIP(hipGetLastError());
@@ -2040,12 +2091,15 @@ static int prove_single(ProveState& S) {
 static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
                       const uint64_t* d_abc, const uint64_t* chal, const uint64_t* rnd, const uint64_t* k1k2,
                       const uint64_t* d_srs, size_t srs_m, int mode, uint64_t* out_pts, uint64_t* out_f,
-                      void* stream) {
+                      void* stream, const uint64_t* d_pub = nullptr, size_t npub = 0) {
   if (!ctx || !d_q || !d_copies || !d_abc || !chal || !rnd || !k1k2 || !d_srs || !out_pts || !out_f)
     return fail(PBF_EINVAL, "null argument");
+  if (npub && !d_pub) return fail(PBF_EINVAL, "null pub with npub > 0");
+  if (npub > n) return fail(PBF_EINVAL, "more public inputs than gates");
   ProveState S(ctx);
   S.mode = mode;
   S.d_q = d_q; S.d_copies = d_copies; S.d_abc = d_abc;
+  S.d_pub = npub ? d_pub : nullptr; S.npub = npub;
   S.out_pts = out_pts; S.out_f = out_f;
   int rc = prove_setup(S, ctx, comm, n, chal, rnd, k1k2, d_srs, srs_m, stream);
   if (rc) return rc;
@@ -2086,6 +2140,46 @@ extern "C" int pbf_plonk_prove_bn254(pbf_ctx* ctx, size_t n, const uint64_t* q, 
   PBF_HIP(hipMemcpyAsync(dsrs.p, srs, srs_m * 64, hipMemcpyHostToDevice, s));
   rc = pbf_plonk_prove_bn254_dev(ctx, n, (const uint64_t*)dq.p, (const uint64_t*)dc.p, (const uint64_t*)dabc.p, chal,
                                  rnd, k1k2, (const uint64_t*)dsrs.p, srs_m, mode, out_pts, out_f, s);
+  if (rc) return rc;
+  PBF_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// Public inputs: pub_i on gate row i < npub (pbf.h). One GPU; npub = 0 is the plain entry.
+extern "C" int pbf_plonk_prove_bn254_pi_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
+                                            const uint64_t* d_abc, const uint64_t* d_pub, size_t npub,
+                                            const uint64_t* chal, const uint64_t* rnd, const uint64_t* k1k2,
+                                            const uint64_t* d_srs, size_t srs_m, int mode, uint64_t* out_pts,
+                                            uint64_t* out_f, void* stream) {
+  return prove_impl(ctx, nullptr, n, d_q, d_copies, d_abc, chal, rnd, k1k2, d_srs, srs_m, mode, out_pts, out_f, stream,
+                    d_pub, npub);
+}
+
+extern "C" int pbf_plonk_prove_bn254_pi(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies,
+                                        const uint64_t* abc, const uint64_t* pub, size_t npub, const uint64_t* chal,
+                                        const uint64_t* rnd, const uint64_t* k1k2, const uint64_t* srs, size_t srs_m,
+                                        int mode, uint64_t* out_pts, uint64_t* out_f) {
+  if (!npub) return pbf_plonk_prove_bn254(ctx, n, q, copies, abc, chal, rnd, k1k2, srs, srs_m, mode, out_pts, out_f);
+  if (!ctx || !q || !copies || !abc || !srs) return fail(PBF_EINVAL, "null argument");
+  if (!pub) return fail(PBF_EINVAL, "null pub with npub > 0");
+  if (npub > n) return fail(PBF_EINVAL, "more public inputs than gates");
+  if (!fr_canonical(pub, npub)) return fail(PBF_EINVAL, "public input not canonical");
+  PBF_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->host_stream();
+  DevBuf &dq = ctx->buf("pv.q"), &dc = ctx->buf("pv.copies"), &dabc = ctx->buf("pv.abc"), &dsrs = ctx->buf("pv.srs"),
+         &dpub = ctx->buf("pv.pub");
+  int rc;
+  if ((rc = dq.ensure(5 * n * 32)) || (rc = dc.ensure(3 * n * 16)) || (rc = dabc.ensure(3 * n * 32)) ||
+      (rc = dsrs.ensure(srs_m * 64)) || (rc = dpub.ensure(npub * 32)))
+    return rc;
+  PBF_HIP(hipMemcpyAsync(dq.p, q, 5 * n * 32, hipMemcpyHostToDevice, s));
+  PBF_HIP(hipMemcpyAsync(dc.p, copies, 3 * n * 16, hipMemcpyHostToDevice, s));
+  PBF_HIP(hipMemcpyAsync(dabc.p, abc, 3 * n * 32, hipMemcpyHostToDevice, s));
+  PBF_HIP(hipMemcpyAsync(dsrs.p, srs, srs_m * 64, hipMemcpyHostToDevice, s));
+  PBF_HIP(hipMemcpyAsync(dpub.p, pub, npub * 32, hipMemcpyHostToDevice, s));
+  rc = pbf_plonk_prove_bn254_pi_dev(ctx, n, (const uint64_t*)dq.p, (const uint64_t*)dc.p, (const uint64_t*)dabc.p,
+                                    (const uint64_t*)dpub.p, npub, chal, rnd, k1k2, (const uint64_t*)dsrs.p, srs_m, mode,
+                                    out_pts, out_f, s);
   if (rc) return rc;
   PBF_HIP(hipStreamSynchronize(s));
   return 0;

@@ -117,4 +117,15 @@ int g1_mul_xyzz_run(const G1Work& w, const uint64_t* d_points, const uint64_t* d
 int verifier_vk(pbf_ctx* ctx, size_t n, const U256& omega, const uint64_t* d_q, const uint64_t* d_copies,
                 const uint64_t* d_srs, size_t srs_m, const uint64_t* k1k2, hipStream_t s, uint64_t pre[8][8]);
 
+// verify_batch.hip: public inputs of the _pi verifiers. pub (host, count x npub canonical values)
+// against the contract of pbf.h: PBF_EINVAL for npub > n, a null pub with npub > 0, a value >= r.
+int plonk_pub_validate(size_t n, const uint64_t* pub, size_t npub, size_t count);
+// d_nd[2 i], d_nd[2 i + 1] = (N_i, D_i), 4 x u64 each in Montgomery form, with
+// sum_{j<npub} pub_ij w^j / (z_i - w^j) = N_i / D_i for proof i < count: d_pub count x npub
+// canonical values, z_i the fourth challenge of d_chal (count x 5); npub, count >= 1. D_i = 0
+// exactly when z_i^n = 1 on some j < npub. PI_i(z_i) = -(z_i^n - 1) n^-1 N_i / D_i:
+// k_vb_pi_partial, k_vb_pi_combine.
+int plonk_pi_fraction_run(pbf_ctx* ctx, const U256& omega, const uint64_t* d_pub, uint64_t npub,
+                          const uint64_t* d_chal, uint64_t count, uint64_t* d_nd, hipStream_t s);
+
 }  // namespace pbf

@@ -1,6 +1,7 @@
 // Plonk::verify over BN254 (src/plonk.rs:468-650): the single-proof verifier and the verification
 // key it shares with the batched verifier (verify_batch.hip). No kernel lives here: the key's
-// sigma labels come from the prover's launcher (prover.hpp sigma_table_run), everything else is
+// sigma labels come from the prover's launcher (prover.hpp sigma_table_run), the public inputs'
+// sum from the batched verifier's (plonk_pi_fraction_run), everything else is
 // host Fr arithmetic, the Fr INTT, two MSMs and one pairing check.
 #include <cstring>
 #include <vector>
@@ -11,26 +12,29 @@ using namespace pbf;
 
 static int verify_with_vk(pbf_ctx* ctx, size_t n, const U256& omega, const uint64_t (*pre)[8], const uint64_t* d_srs,
                           const uint64_t* g2, const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* chal,
-                          const uint64_t* u_in, const uint64_t* k1k2, int mode, int* ok, hipStream_t s);
+                          const uint64_t* u_in, const uint64_t* k1k2, int mode, const U256* pi_nd, int* ok,
+                          hipStream_t s);
 
 // Plonk::verify (src/plonk.rs:468-650). srs: >= n affine G1 points (g1s, device), g2: [g2_1, g2_s]
 // (2 x 16 u64, host); proof as pbf_plonk_prove_bn254 returns it; u the verifier's random
 // scalar (rand[0], plonk.rs:519). mode 0 keeps step 7's t_z (plonk.rs:575-581, no alpha on
 // the permutation term), mode 1 the paper's. *ok = 1 iff e(E1, [s]G2) == e(E2, G2).
-extern "C" int pbf_plonk_verify_bn254_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
-                                          const uint64_t* d_srs, size_t srs_m, const uint64_t* g2,
-                                          const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* chal,
-                                          const uint64_t* u_in, const uint64_t* k1k2, int mode, int* ok, void* stream) {
+// pub, npub: the public inputs of pbf_plonk_verify_bn254_pi* (host; none: null, 0)
+static int verify_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies, const uint64_t* d_srs,
+                      size_t srs_m, const uint64_t* g2, const uint64_t* proof_pts, const uint64_t* proof_f,
+                      const uint64_t* pub, size_t npub, const uint64_t* chal, const uint64_t* u_in, const uint64_t* k1k2,
+                      int mode, int* ok, void* stream) {
   if (!ctx || !d_q || !d_copies || !d_srs || !g2 || !proof_pts || !proof_f || !chal || !u_in || !k1k2 || !ok)
     return fail(PBF_EINVAL, "null argument");
   *ok = 0;
   if (n < 8 || (n & (n - 1))) return fail(PBF_EINVAL, "n must be a power of two >= 8");
   if (srs_m < n) return fail(PBF_EINVAL, "SRS too short");
+  int rc;
+  if ((rc = plonk_pub_validate(n, pub, npub, 1))) return rc;
   PBF_HIP(hipSetDevice(ctx->device));
   uint32_t log_n = 0;
   while ((1ull << log_n) < n) ++log_n;
   hipStream_t s = (hipStream_t)stream;
-  int rc;
   // Step 1-2: proof points on the curve, proof fields canonical (plonk.rs:523-547)
   for (int i = 0; i < 9; ++i)
     if (!on_curve(proof_pts + 8 * i)) return 0;
@@ -39,7 +43,41 @@ extern "C" int pbf_plonk_verify_bn254_dev(pbf_ctx* ctx, size_t n, const uint64_t
   const U256 omega = fr_root_of_unity(log_n);
   uint64_t pre[8][8];
   if ((rc = verifier_vk(ctx, n, omega, d_q, d_copies, d_srs, srs_m, k1k2, s, pre))) return rc;
-  return verify_with_vk(ctx, n, omega, pre, d_srs, g2, proof_pts, proof_f, chal, u_in, k1k2, mode, ok, s);
+  // public inputs: sum_j pub_j w^j / (z - w^j) as a fraction (N, D), from the batched verifier's
+  // kernels with count = 1
+  U256 nd[2];
+  if (npub) {
+    DevBuf &dp = ctx->buf("vf.pub"), &dz = ctx->buf("vf.pichal"), &dn = ctx->buf("vf.pind");
+    if ((rc = dp.ensure(npub * 32)) || (rc = dz.ensure(5 * 32)) || (rc = dn.ensure(64))) return rc;
+    PBF_HIP(hipMemcpyAsync(dp.p, pub, npub * 32, hipMemcpyHostToDevice, s));
+    PBF_HIP(hipMemcpyAsync(dz.p, chal, 5 * 32, hipMemcpyHostToDevice, s));
+    if ((rc = plonk_pi_fraction_run(ctx, omega, (const uint64_t*)dp.p, npub, (const uint64_t*)dz.p, 1, (uint64_t*)dn.p, s)))
+      return rc;
+    uint64_t h[8];
+    PBF_HIP(hipMemcpyAsync(h, dn.p, sizeof(h), hipMemcpyDeviceToHost, s));
+    PBF_HIP(hipStreamSynchronize(s));
+    nd[0] = u256_from_u64(h);  // Montgomery form as stored
+    nd[1] = u256_from_u64(h + 4);
+  }
+  return verify_with_vk(ctx, n, omega, pre, d_srs, g2, proof_pts, proof_f, chal, u_in, k1k2, mode, npub ? nd : nullptr,
+                        ok, s);
+}
+
+extern "C" int pbf_plonk_verify_bn254_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
+                                          const uint64_t* d_srs, size_t srs_m, const uint64_t* g2,
+                                          const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* chal,
+                                          const uint64_t* u_in, const uint64_t* k1k2, int mode, int* ok, void* stream) {
+  return verify_dev(ctx, n, d_q, d_copies, d_srs, srs_m, g2, proof_pts, proof_f, nullptr, 0, chal, u_in, k1k2, mode, ok,
+                    stream);
+}
+
+extern "C" int pbf_plonk_verify_bn254_pi_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
+                                             const uint64_t* d_srs, size_t srs_m, const uint64_t* g2,
+                                             const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* pub,
+                                             size_t npub, const uint64_t* chal, const uint64_t* u_in,
+                                             const uint64_t* k1k2, int mode, int* ok, void* stream) {
+  return verify_dev(ctx, n, d_q, d_copies, d_srs, srs_m, g2, proof_pts, proof_f, pub, npub, chal, u_in, k1k2, mode, ok,
+                    stream);
 }
 
 // Plonk::verify's preprocessing, shared by the single and the batched verifier
@@ -111,10 +149,12 @@ int pbf::verifier_vk(pbf_ctx* ctx, size_t n, const U256& omega, const uint64_t* 
   return 0;
 }
 
-// Plonk::verify steps 4-12 for one proof whose points and fields passed steps 1-2
+// Plonk::verify steps 4-12 for one proof whose points and fields passed steps 1-2. pi_nd: null, or
+// the public inputs' fraction (N, D) of plonk_pi_fraction_run: step 7 then takes r_z + PI(z)
 static int verify_with_vk(pbf_ctx* ctx, size_t n, const U256& omega, const uint64_t (*pre)[8], const uint64_t* d_srs,
                           const uint64_t* g2, const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* chal,
-                          const uint64_t* u_in, const uint64_t* k1k2, int mode, int* ok, hipStream_t s) {
+                          const uint64_t* u_in, const uint64_t* k1k2, int mode, const U256* pi_nd, int* ok,
+                          hipStream_t s) {
   const U256 one = fr_one_m();
   const U256 k1 = hm(k1k2), k2 = hm(k1k2 + 4);
   int rc;
@@ -139,7 +179,9 @@ static int verify_with_vk(pbf_ctx* ctx, size_t n, const U256& omega, const uint6
                               Fr::add(Fr::add(b_z, Fr::mul(beta, s2_z)), gamma)),
                       Fr::mul(Fr::add(c_z, gamma), zw_z));
   if (mode == 1) perm = Fr::mul(perm, alpha);
-  const U256 t_z = Fr::mul(Fr::sub(Fr::sub(r_z, perm), Fr::mul(l1, alpha2)), fr_inv(z_h_z));
+  U256 rpi_z = r_z;  // r_z + PI(z), PI(z) = -Z_H(z) n^-1 N / D (D != 0: z is not in H here)
+  if (pi_nd) rpi_z = Fr::sub(r_z, Fr::mul(Fr::mul(Fr::mul(z_h_z, fr_inv(hm64(n))), pi_nd[0]), fr_inv(pi_nd[1])));
+  const U256 t_z = Fr::mul(Fr::sub(Fr::sub(rpi_z, perm), Fr::mul(l1, alpha2)), fr_inv(z_h_z));
   // Steps 8-10 as one linear combination of points (bases / scalars)
   U256 vp[7];
   vp[0] = one;
@@ -212,7 +254,18 @@ extern "C" int pbf_plonk_verify_bn254(pbf_ctx* ctx, size_t n, const uint64_t* q,
                                       const uint64_t* srs, size_t srs_m, const uint64_t* g2, const uint64_t* proof_pts,
                                       const uint64_t* proof_f, const uint64_t* chal, const uint64_t* u,
                                       const uint64_t* k1k2, int mode, int* ok) {
+  return pbf_plonk_verify_bn254_pi(ctx, n, q, copies, srs, srs_m, g2, proof_pts, proof_f, nullptr, 0, chal, u, k1k2, mode,
+                                   ok);
+}
+
+extern "C" int pbf_plonk_verify_bn254_pi(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies,
+                                         const uint64_t* srs, size_t srs_m, const uint64_t* g2,
+                                         const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* pub,
+                                         size_t npub, const uint64_t* chal, const uint64_t* u, const uint64_t* k1k2,
+                                         int mode, int* ok) {
   if (!ctx || !q || !copies || !srs) return fail(PBF_EINVAL, "null argument");
+  int rc0 = plonk_pub_validate(n, pub, npub, 1);  // before the uploads
+  if (rc0) return rc0;
   PBF_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->host_stream();
   DevBuf &dq = ctx->buf("vf.q"), &dc = ctx->buf("vf.copies"), &dsrs = ctx->buf("vf.srs");
@@ -221,6 +274,6 @@ extern "C" int pbf_plonk_verify_bn254(pbf_ctx* ctx, size_t n, const uint64_t* q,
   PBF_HIP(hipMemcpyAsync(dq.p, q, 5 * n * 32, hipMemcpyHostToDevice, s));
   PBF_HIP(hipMemcpyAsync(dc.p, copies, 3 * n * 16, hipMemcpyHostToDevice, s));
   PBF_HIP(hipMemcpyAsync(dsrs.p, srs, srs_m * 64, hipMemcpyHostToDevice, s));
-  return pbf_plonk_verify_bn254_dev(ctx, n, (const uint64_t*)dq.p, (const uint64_t*)dc.p, (const uint64_t*)dsrs.p,
-                                    srs_m, g2, proof_pts, proof_f, chal, u, k1k2, mode, ok, s);
+  return verify_dev(ctx, n, (const uint64_t*)dq.p, (const uint64_t*)dc.p, (const uint64_t*)dsrs.p, srs_m, g2, proof_pts,
+                    proof_f, pub, npub, chal, u, k1k2, mode, ok, s);
 }

@@ -16,6 +16,9 @@
 //   k_vb_scalars  one lane per PROOF (blocks of one wave): fields canonical, Z_H(z) != 0, then
 //                 the single verifier's Fr formulas (steps 4-10) scaled by rho_i; a flagged
 //                 proof's scalars are written as zero, so its points ride through the MSM inert
+//   k_vb_pi_*     public inputs (the _pi entries): sum_j pub_ij w^j / (z_i - w^j) of every proof as
+//                 one fraction (N_i, D_i): a wave per (chunk of 256 inputs, proof), then a wave per
+//                 proof over its chunks; k_vb_scalars folds D_i into its one inversion
 //   k_vb_colsum*  the 9 shared-base scalars of an index range [lo, hi): LDS tree per block,
 //                 second step across blocks (field addition is exact: any order, same limbs)
 // Every scalar is the canonical value the host formulas give. Localisation (ok_each) halves the
@@ -94,10 +97,13 @@ __global__ void __launch_bounds__(256) k_vb_curve(const uint64_t* pts, uint32_t 
 //   sc[9 i + j]      j < 9: a b c z t_lo t_mid t_hi w_z w_zw
 //   e1s[E1_N i + E1_AT + 0, 1]  rho, rho u
 //   contrib[j][i]    j < 9: q_m q_l q_r q_o q_c s1 s2 (-d3 on s3) (-E on G)
+// PI: step 7 takes r_z + PI(z) with PI(z) = -Z_H(z) n^-1 N_i / D_i from pi_nd (k_vb_pi_*); D_i
+// joins the one inversion (3 products more). PI = false is the kernel of the plain entries.
+template <bool PI>
 __global__ void __launch_bounds__(64) k_vb_scalars(const uint64_t* __restrict__ pf, const uint64_t* __restrict__ chal,
                                                    const uint64_t* __restrict__ u_in, const uint64_t* __restrict__ rho_in,
-                                                   VbParams P, int* flag, uint64_t* sc, uint64_t* e1s,
-                                                   uint64_t* contrib) {
+                                                   const uint64_t* __restrict__ pi_nd, VbParams P, int* flag,
+                                                   uint64_t* sc, uint64_t* e1s, uint64_t* contrib) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= P.count) return;
   const uint64_t* f = pf + 28 * (uint64_t)i;
@@ -127,7 +133,17 @@ __global__ void __launch_bounds__(64) k_vb_scalars(const uint64_t* __restrict__ 
   // Step 5: L_1(z) = (z^n - 1) / (n (z - 1)); z = 1 has Z_H = 0 and never gets here, so one
   // inversion of Z_H(z) (z - 1) serves both quotients
   const U256 zm1 = Fr::sub(zc, one);
-  const U256 tinv = vb_inv(fmul(z_h_z, zm1), one);
+  const U256 zhm = fmul(z_h_z, zm1);
+  U256 tinv, rpi_z = r_z;  // r_z + PI(z)
+  if (PI) {
+    // D_i = prod_j (z w^-j - 1) is nonzero here: a zero factor is z in H, flagged above
+    const U256 piN = u256_from_u64(pi_nd + 8 * (uint64_t)i), piD = u256_from_u64(pi_nd + 8 * (uint64_t)i + 4);
+    const U256 all = vb_inv(fmul(zhm, piD), one);
+    tinv = fmul(all, piD);
+    rpi_z = Fr::sub(r_z, fmul(fmul(fmul(z_h_z, P.n_inv), piN), fmul(all, zhm)));
+  } else {
+    tinv = vb_inv(zhm, one);
+  }
   const U256 inv_zh = fmul(tinv, zm1);
   const U256 l1 = fmul(fmul(z_h_z, fmul(tinv, z_h_z)), P.n_inv);
   // Step 7: t_z
@@ -138,7 +154,7 @@ __global__ void __launch_bounds__(64) k_vb_scalars(const uint64_t* __restrict__ 
   const U256 pab = fmul(pa, pb);
   U256 perm = fmul(pab, fmul(Fr::add(c_z, gamma), zw_z));
   if (P.mode == 1) perm = fmul(perm, alpha);
-  const U256 t_z = fmul(Fr::sub(Fr::sub(r_z, perm), l1a2), inv_zh);
+  const U256 t_z = fmul(Fr::sub(Fr::sub(rpi_z, perm), l1a2), inv_zh);
   // Steps 8-10
   U256 vp[7];
   vp[0] = one;
@@ -187,6 +203,90 @@ __global__ void __launch_bounds__(64) k_vb_scalars(const uint64_t* __restrict__ 
   stm(c + 6 * cs, fmul(rho, vp[6]));              // s2
   stm(c + 7 * cs, Fr::sub(zero, fmul(rho, d3)));  // - s3 d3
   stm(c + 8 * cs, Fr::sub(zero, fmul(rho, ecoef)));  // - E
+}
+
+// ---- public inputs: PI(z) = -(z^n - 1)/n * S, S = sum_{j<npub} pub_j w^j / (z - w^j) = sum_j pub_j / (z w^-j - 1)
+// S is kept as a fraction (N, D): adding the term p / d is (N, D) <- (N d + p D, D d), two
+// fractions add as (N1 D2 + N2 D1, D1 D2); no inversion until k_vb_scalars' one. Field sums and
+// products are exact, so every order of combination gives the same value N / D. z in H makes a d
+// zero and with it D (and N / D meaningless): the kernels run through, and k_vb_scalars never
+// reads the fraction of such a proof (flag bit 4).
+constexpr uint32_t PI_PER = 4, PI_BLK = 64 * PI_PER;  // one wave per chunk: lane l takes j = chunk PI_BLK + l + 64 k
+constexpr int PI_VBITS = 20;                          // chunks < 2^20 (npub <= n <= 2^26)
+struct PiPow {
+  U256 step;          // w^-64
+  U256 tl[64];        // w^-l
+  U256 tv[PI_VBITS];  // w^-(PI_BLK 2^k)
+};
+static_assert(sizeof(PiPow) + 64 <= 4096, "kernel argument limit");
+
+// the wave's fractions added up through LDS (shN, shD: 64 values each); the sum on every lane
+__device__ __forceinline__ void pi_wave_sum(U256* shN, U256* shD, U256& N, U256& D) {
+  const uint32_t t = threadIdx.x;
+  shN[t] = N;
+  shD[t] = D;
+  __syncthreads();
+  for (uint32_t s = 32; s; s >>= 1) {
+    if (t < s) {
+      const U256 n1 = shN[t], d1 = shD[t], n2 = shN[t + s], d2 = shD[t + s];
+      shN[t] = Fr::add(fmul(n1, d2), fmul(n2, d1));
+      shD[t] = fmul(d1, d2);
+    }
+    __syncthreads();
+  }
+  N = shN[0];
+  D = shD[0];
+}
+
+// part[proof chunks + chunk] = (N, D) of the chunk's terms, Montgomery form; grid chunks x count
+// (flat, chunk fastest), one wave. R-degrees: x = z w^-j and d at 1, N at 1, pub as stored (0), so
+// D is carried at degree 2 (pub D lands at 1 with no conversion of pub) and lowered once at the end.
+__global__ void __launch_bounds__(64) k_vb_pi_partial(const uint64_t* __restrict__ pub, const uint64_t* __restrict__ chal,
+                                                      uint32_t npub, uint32_t chunks, PiPow pw, uint64_t* part) {
+  __shared__ U256 shN[64], shD[64];
+  const uint32_t l = threadIdx.x, v = blockIdx.x % chunks;
+  const uint64_t proof = blockIdx.x / chunks;
+  const U256 one = Fr::to_mont(Fr::one_plain());
+  U256 N = u256_zero(), D = one;
+  uint64_t j = (uint64_t)v * PI_BLK + l;
+  if (j < npub) {
+    U256 x = fmul(ldm(chal + 20 * proof + 12), pw.tl[l]);
+    for (uint32_t k = 0, vv = v; vv; vv >>= 1, ++k)
+      if (vv & 1) x = fmul(x, pw.tv[k]);
+    U256 D2 = Fr::to_mont(one);
+    const uint64_t* p = pub + 4 * (proof * npub + j);
+    for (uint32_t k = 0; k < PI_PER && j < npub; ++k, j += 64, p += 4 * 64) {
+      const U256 d = Fr::sub(x, one);
+      N = Fr::add(fmul(N, d), fmul(u256_from_u64(p), D2));
+      D2 = fmul(D2, d);
+      x = fmul(x, pw.step);
+    }
+    D = Fr::from_mont(D2);
+  }
+  pi_wave_sum(shN, shD, N, D);
+  if (l == 0) {
+    uint64_t* o = part + 8 * (uint64_t)blockIdx.x;
+    u256_to_u64(N, o);
+    u256_to_u64(D, o + 4);
+  }
+}
+
+// nd[proof] = the sum of the proof's `chunks` partial fractions; grid count, one wave
+__global__ void __launch_bounds__(64) k_vb_pi_combine(const uint64_t* __restrict__ part, uint32_t chunks, uint64_t* nd) {
+  __shared__ U256 shN[64], shD[64];
+  const uint64_t proof = blockIdx.x;
+  U256 N = u256_zero(), D = Fr::to_mont(Fr::one_plain());
+  for (uint32_t c = threadIdx.x; c < chunks; c += 64) {
+    const uint64_t* p = part + 8 * (proof * chunks + c);
+    const U256 n2 = u256_from_u64(p), d2 = u256_from_u64(p + 4);
+    N = Fr::add(fmul(N, d2), fmul(n2, D));
+    D = fmul(D, d2);
+  }
+  pi_wave_sum(shN, shD, N, D);
+  if (threadIdx.x == 0) {
+    u256_to_u64(N, nd + 8 * proof);
+    u256_to_u64(D, nd + 8 * proof + 4);
+  }
 }
 
 // canonical residues add like any others: no Montgomery conversion in the sums (fr_block_sum)
@@ -294,13 +394,51 @@ int vb_validate(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copie
 
 }  // namespace
 
-extern "C" int pbf_plonk_verify_bn254_batch_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
-                                                const uint64_t* d_srs, size_t srs_m, const uint64_t* g2, size_t count,
-                                                const uint64_t* proof_pts, const uint64_t* proof_f,
-                                                const uint64_t* chal, const uint64_t* u, const uint64_t* rho,
-                                                const uint64_t* k1k2, int mode, int* ok, int* ok_each, void* stream) {
+// prover.hpp: the public-input fractions of `count` proofs, for both verifiers
+int pbf::plonk_pi_fraction_run(pbf_ctx* ctx, const U256& omega, const uint64_t* d_pub, uint64_t npub,
+                               const uint64_t* d_chal, uint64_t count, uint64_t* d_nd, hipStream_t s) {
+  const uint64_t chunks = (npub + PI_BLK - 1) / PI_BLK;
+  if (!chunks || !count) return fail(PBF_EINVAL, "no public input");
+  if (chunks >> PI_VBITS || count * chunks > 0x7fffffffull)
+    return fail(PBF_EINVAL, "count x npub exceeds one launch of the public-input kernels");
+  uint64_t* part = d_nd;  // one chunk: its fraction is the proof's
+  if (chunks > 1) {
+    DevBuf& pb = ctx->buf("vb.pipart");
+    int rc = pb.ensure(count * chunks * 64);
+    if (rc) return rc;
+    part = (uint64_t*)pb.p;
+  }
+  PiPow pw;
+  const U256 wi = fr_inv(omega);
+  pw.step = fr_pow(wi, 64);
+  pw.tl[0] = fr_one_m();
+  for (int l = 1; l < 64; ++l) pw.tl[l] = Fr::mul(pw.tl[l - 1], wi);
+  pw.tv[0] = fr_pow(wi, PI_BLK);
+  for (int k = 1; k < PI_VBITS; ++k) pw.tv[k] = Fr::mul(pw.tv[k - 1], pw.tv[k - 1]);
+  hipLaunchKernelGGL(k_vb_pi_partial, dim3((uint32_t)(count * chunks)), dim3(64), 0, s, d_pub, d_chal, (uint32_t)npub,
+                     (uint32_t)chunks, pw, part);
+  if (chunks > 1)
+    hipLaunchKernelGGL(k_vb_pi_combine, dim3((uint32_t)count), dim3(64), 0, s, (const uint64_t*)part, (uint32_t)chunks,
+                       d_nd);
+  PBF_HIP(hipGetLastError());
+  return 0;
+}
+
+// pub of the _pi verifiers: host values, checked before anything is enqueued
+int pbf::plonk_pub_validate(size_t n, const uint64_t* pub, size_t npub, size_t count) {
+  if (npub > n) return fail(PBF_EINVAL, "more public inputs than gates");
+  if (npub && !pub) return fail(PBF_EINVAL, "null pub with npub > 0");
+  if (npub && !fr_canonical(pub, count * npub)) return fail(PBF_EINVAL, "public input not canonical");
+  return 0;
+}
+
+static int vb_run(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies, const uint64_t* d_srs,
+                  size_t srs_m, const uint64_t* g2, size_t count, const uint64_t* proof_pts, const uint64_t* proof_f,
+                  const uint64_t* pub, size_t npub, const uint64_t* chal, const uint64_t* u, const uint64_t* rho,
+                  const uint64_t* k1k2, int mode, int* ok, int* ok_each, void* stream) {
   int rc;
-  if ((rc = vb_validate(ctx, n, d_q, d_copies, d_srs, srs_m, g2, count, proof_pts, proof_f, chal, u, rho, k1k2, ok)))
+  if ((rc = vb_validate(ctx, n, d_q, d_copies, d_srs, srs_m, g2, count, proof_pts, proof_f, chal, u, rho, k1k2, ok)) ||
+      (rc = plonk_pub_validate(n, pub, npub, count)))
     return rc;
   PBF_HIP(hipSetDevice(ctx->device));
   uint32_t log_n = 0;
@@ -349,9 +487,21 @@ extern "C" int pbf_plonk_verify_bn254_batch_dev(pbf_ctx* ctx, size_t n, const ui
   const uint32_t npts = (uint32_t)(9 * c);
   hipLaunchKernelGGL(k_vb_curve, dim3((npts + 255) / 256), dim3(256), 0, s, (const uint64_t*)pts, npts, (int*)bfl.p,
                      (uint64_t*)bq.p);
-  hipLaunchKernelGGL(k_vb_scalars, dim3((uint32_t)((c + 63) / 64)), dim3(64), 0, s, (const uint64_t*)bf.p,
-                     (const uint64_t*)bc.p, (const uint64_t*)bu.p, (const uint64_t*)br.p, P, (int*)bfl.p,
-                     (uint64_t*)bs.p, (uint64_t*)bt.p, (uint64_t*)bk.p);
+  if (npub) {  // once per call: localisation reuses the per-proof scalars
+    DevBuf &bpub = ctx->buf("vb.pub"), &bnd = ctx->buf("vb.pind");
+    if ((rc = bpub.ensure(c * npub * 32)) || (rc = bnd.ensure(c * 64))) return rc;
+    PBF_HIP(hipMemcpyAsync(bpub.p, pub, c * npub * 32, hipMemcpyHostToDevice, s));
+    if ((rc = plonk_pi_fraction_run(ctx, omega, (const uint64_t*)bpub.p, npub, (const uint64_t*)bc.p, c,
+                                    (uint64_t*)bnd.p, s)))
+      return rc;
+    hipLaunchKernelGGL(k_vb_scalars<true>, dim3((uint32_t)((c + 63) / 64)), dim3(64), 0, s, (const uint64_t*)bf.p,
+                       (const uint64_t*)bc.p, (const uint64_t*)bu.p, (const uint64_t*)br.p, (const uint64_t*)bnd.p, P,
+                       (int*)bfl.p, (uint64_t*)bs.p, (uint64_t*)bt.p, (uint64_t*)bk.p);
+  } else {
+    hipLaunchKernelGGL(k_vb_scalars<false>, dim3((uint32_t)((c + 63) / 64)), dim3(64), 0, s, (const uint64_t*)bf.p,
+                       (const uint64_t*)bc.p, (const uint64_t*)bu.p, (const uint64_t*)br.p, (const uint64_t*)nullptr, P,
+                       (int*)bfl.p, (uint64_t*)bs.p, (uint64_t*)bt.p, (uint64_t*)bk.p);
+  }
   PBF_HIP(hipGetLastError());
   std::vector<int> hflag(c);
   PBF_HIP(hipMemcpyAsync(hflag.data(), bfl.p, c * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -372,13 +522,42 @@ extern "C" int pbf_plonk_verify_bn254_batch_dev(pbf_ctx* ctx, size_t n, const ui
   return B.localise(mid, c, left, &right);
 }
 
+extern "C" int pbf_plonk_verify_bn254_batch_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
+                                                const uint64_t* d_srs, size_t srs_m, const uint64_t* g2, size_t count,
+                                                const uint64_t* proof_pts, const uint64_t* proof_f,
+                                                const uint64_t* chal, const uint64_t* u, const uint64_t* rho,
+                                                const uint64_t* k1k2, int mode, int* ok, int* ok_each, void* stream) {
+  return vb_run(ctx, n, d_q, d_copies, d_srs, srs_m, g2, count, proof_pts, proof_f, nullptr, 0, chal, u, rho, k1k2, mode,
+                ok, ok_each, stream);
+}
+
+extern "C" int pbf_plonk_verify_bn254_batch_pi_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
+                                                   const uint64_t* d_srs, size_t srs_m, const uint64_t* g2, size_t count,
+                                                   const uint64_t* proof_pts, const uint64_t* proof_f,
+                                                   const uint64_t* pub, size_t npub, const uint64_t* chal,
+                                                   const uint64_t* u, const uint64_t* rho, const uint64_t* k1k2, int mode,
+                                                   int* ok, int* ok_each, void* stream) {
+  return vb_run(ctx, n, d_q, d_copies, d_srs, srs_m, g2, count, proof_pts, proof_f, pub, npub, chal, u, rho, k1k2, mode,
+                ok, ok_each, stream);
+}
+
 extern "C" int pbf_plonk_verify_bn254_batch(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies,
                                             const uint64_t* srs, size_t srs_m, const uint64_t* g2, size_t count,
                                             const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* chal,
                                             const uint64_t* u, const uint64_t* rho, const uint64_t* k1k2, int mode,
                                             int* ok, int* ok_each) {
+  return pbf_plonk_verify_bn254_batch_pi(ctx, n, q, copies, srs, srs_m, g2, count, proof_pts, proof_f, nullptr, 0, chal,
+                                         u, rho, k1k2, mode, ok, ok_each);
+}
+
+extern "C" int pbf_plonk_verify_bn254_batch_pi(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies,
+                                               const uint64_t* srs, size_t srs_m, const uint64_t* g2, size_t count,
+                                               const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* pub,
+                                               size_t npub, const uint64_t* chal, const uint64_t* u, const uint64_t* rho,
+                                               const uint64_t* k1k2, int mode, int* ok, int* ok_each) {
   int rc;
-  if ((rc = vb_validate(ctx, n, q, copies, srs, srs_m, g2, count, proof_pts, proof_f, chal, u, rho, k1k2, ok)))
+  if ((rc = vb_validate(ctx, n, q, copies, srs, srs_m, g2, count, proof_pts, proof_f, chal, u, rho, k1k2, ok)) ||
+      (rc = plonk_pub_validate(n, pub, npub, count)))
     return rc;
   PBF_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->host_stream();
@@ -387,7 +566,6 @@ extern "C" int pbf_plonk_verify_bn254_batch(pbf_ctx* ctx, size_t n, const uint64
   PBF_HIP(hipMemcpyAsync(dq.p, q, 5 * n * 32, hipMemcpyHostToDevice, s));
   PBF_HIP(hipMemcpyAsync(dc.p, copies, 3 * n * 16, hipMemcpyHostToDevice, s));
   PBF_HIP(hipMemcpyAsync(dsrs.p, srs, srs_m * 64, hipMemcpyHostToDevice, s));
-  return pbf_plonk_verify_bn254_batch_dev(ctx, n, (const uint64_t*)dq.p, (const uint64_t*)dc.p,
-                                          (const uint64_t*)dsrs.p, srs_m, g2, count, proof_pts, proof_f, chal, u, rho,
-                                          k1k2, mode, ok, ok_each, s);
+  return vb_run(ctx, n, (const uint64_t*)dq.p, (const uint64_t*)dc.p, (const uint64_t*)dsrs.p, srs_m, g2, count,
+                proof_pts, proof_f, pub, npub, chal, u, rho, k1k2, mode, ok, ok_each, s);
 }

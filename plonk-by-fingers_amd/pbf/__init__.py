@@ -87,6 +87,21 @@ SIGNATURES = [
     ("pbf_plonk_verify_bn254_batch_dev", ctypes.c_int, [_vp, _sz, _vp, _vp, _vp, _sz, _p64, _sz, _p64, _p64, _p64,
                                                         _p64, _p64, _p64, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                                         ctypes.POINTER(ctypes.c_int), _vp]),
+    ("pbf_plonk_prove_bn254_pi", ctypes.c_int, [_vp, _sz, _p64, _p64, _p64, _p64, _sz, _p64, _p64, _p64, _p64, _sz,
+                                                ctypes.c_int, _p64, _p64]),
+    ("pbf_plonk_prove_bn254_pi_dev", ctypes.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, _sz, _p64, _p64, _p64, _vp, _sz,
+                                                    ctypes.c_int, _p64, _p64, _vp]),
+    ("pbf_plonk_verify_bn254_pi", ctypes.c_int, [_vp, _sz, _p64, _p64, _p64, _sz, _p64, _p64, _p64, _p64, _sz, _p64,
+                                                 _p64, _p64, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    ("pbf_plonk_verify_bn254_pi_dev", ctypes.c_int, [_vp, _sz, _vp, _vp, _vp, _sz, _p64, _p64, _p64, _p64, _sz, _p64,
+                                                     _p64, _p64, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _vp]),
+    ("pbf_plonk_verify_bn254_batch_pi", ctypes.c_int, [_vp, _sz, _p64, _p64, _p64, _sz, _p64, _sz, _p64, _p64, _p64,
+                                                       _sz, _p64, _p64, _p64, _p64, ctypes.c_int,
+                                                       ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    ("pbf_plonk_verify_bn254_batch_pi_dev", ctypes.c_int, [_vp, _sz, _vp, _vp, _vp, _sz, _p64, _sz, _p64, _p64, _p64,
+                                                           _sz, _p64, _p64, _p64, _p64, ctypes.c_int,
+                                                           ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                                           _vp]),
     ("pbf_plonk_prove_bn254_sharded_dev", ctypes.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _p64, _p64, _p64, _vp, _sz,
                                                          ctypes.c_int, _p64, _p64, _vp]),
     ("pbf_plonk_synth_circuit_bn254_dev", ctypes.c_int, [_vp, _sz, _u64, _vp, _vp, _vp, _vp]),
@@ -523,6 +538,120 @@ class Context:
                                                          _ptr(_g2_limbs(g2s)), count, _ptr(pa), _ptr(fa), _ptr(cha),
                                                          _ptr(ua), _ptr(ra), _ptr(ints_to_limbs(k1k2)), mode,
                                                          ctypes.byref(ok), oe, stream))
+        return (ok.value == 1, [bool(v) for v in oe[:count]]) if each else ok.value == 1
+
+    # ---- public inputs (include/pbf.h "Public inputs"): pub_i on gate row i < npub, one circuit for
+    # many statements. pub: ints (or None with npub = 0); npub defaults to len(pub).
+    @staticmethod
+    def _pub_arg(pub, npub):
+        """(limb array kept alive by the caller, its pointer or None, npub) of one statement."""
+        if pub is None:
+            return None, None, (0 if npub is None else npub)
+        a = ints_to_limbs(list(pub))
+        return a, (_ptr(a) if len(a) else None), (len(pub) if npub is None else npub)
+
+    @staticmethod
+    def _batch_pub(pubs):
+        """count x npub x 4 limbs, proof-major and compact, of a batch's public inputs (one list per
+        proof, all of one length); returns (array, npub)."""
+        npub = len(pubs[0]) if pubs else 0
+        if any(len(p) != npub for p in pubs):
+            raise ValueError("every proof of a batch has the same number of public inputs")
+        return ints_to_limbs([x for p in pubs for x in p]), npub
+
+    def plonk_prove_bn254_pi(self, q, copies, abc, pub, chal, rnd, srs, k1k2=(2, 3), mode=0, npub=None):
+        """plonk_prove_bn254 with public inputs: row i < npub satisfies ... + q_c - pub_i = 0."""
+        n = len(abc[0])
+        qa = ints_to_limbs([x for col in q for x in col])
+        ca = np.array([v for col in copies for (k, i) in col for v in (k, i)], dtype=np.uint64)
+        aa = ints_to_limbs([x for col in abc for x in col])
+        sa = _g1_limbs(srs)
+        _keep, pp, npub = self._pub_arg(pub, npub)
+        pts = np.zeros(72, dtype=np.uint64)
+        fs = np.zeros(28, dtype=np.uint64)
+        _check(self.lib.pbf_plonk_prove_bn254_pi(self.h, n, _ptr(qa), _ptr(ca), _ptr(aa), pp, npub,
+                                                 _ptr(ints_to_limbs(chal)), _ptr(ints_to_limbs(rnd)),
+                                                 _ptr(ints_to_limbs(k1k2)), _ptr(sa), len(srs), mode, _ptr(pts),
+                                                 _ptr(fs)))
+        pv = limbs_to_ints(pts)
+        return [None if pv[2 * i] == 0 and pv[2 * i + 1] == 0 else (pv[2 * i], pv[2 * i + 1]) for i in range(9)], \
+            limbs_to_ints(fs)
+
+    def plonk_prove_bn254_pi_dev(self, n, d_q, d_copies, d_abc, d_pub, npub, chal, rnd, d_srs, srs_m, k1k2=(2, 3),
+                                 mode=0, stream: int = 0):
+        """The same on device inputs; d_pub: npub x 4 u64 on the device (0 / None with npub = 0)."""
+        pts = np.zeros(72, dtype=np.uint64)
+        fs = np.zeros(28, dtype=np.uint64)
+        _check(self.lib.pbf_plonk_prove_bn254_pi_dev(self.h, n, d_q, d_copies, d_abc, d_pub or None, npub,
+                                                     _ptr(ints_to_limbs(chal)), _ptr(ints_to_limbs(rnd)),
+                                                     _ptr(ints_to_limbs(k1k2)), d_srs, srs_m, mode, _ptr(pts), _ptr(fs),
+                                                     stream))
+        return pts, fs
+
+    def plonk_verify_bn254_pi(self, q, copies, srs, g2s, pts, fields, pub, chal, u, k1k2=(2, 3), mode=0,
+                              npub=None) -> bool:
+        n = len(q[0])
+        qa = ints_to_limbs([x for col in q for x in col])
+        ca = np.array([v for col in copies for (k, i) in col for v in (k, i)], dtype=np.uint64)
+        sa = _g1_limbs(srs)
+        _keep, pp, npub = self._pub_arg(pub, npub)
+        ok = ctypes.c_int(-1)
+        _check(self.lib.pbf_plonk_verify_bn254_pi(self.h, n, _ptr(qa), _ptr(ca), _ptr(sa), len(srs),
+                                                  _ptr(_g2_limbs(g2s)), _ptr(_g1_limbs(pts)),
+                                                  _ptr(ints_to_limbs(fields)), pp, npub, _ptr(ints_to_limbs(chal)),
+                                                  _ptr(ints_to_limbs([u])), _ptr(ints_to_limbs(k1k2)), mode,
+                                                  ctypes.byref(ok)))
+        return ok.value == 1
+
+    def plonk_verify_bn254_pi_dev(self, n, d_q, d_copies, d_srs, srs_m, g2s, pts, fields, pub, chal, u, k1k2=(2, 3),
+                                  mode=0, stream: int = 0, npub=None) -> bool:
+        """The circuit and SRS on the device; the proof and pub on the host."""
+        pa = pts if isinstance(pts, np.ndarray) else _g1_limbs(pts)
+        fa = fields if isinstance(fields, np.ndarray) else ints_to_limbs(fields)
+        _keep, pp, npub = self._pub_arg(pub, npub)
+        ok = ctypes.c_int(-1)
+        _check(self.lib.pbf_plonk_verify_bn254_pi_dev(self.h, n, d_q, d_copies, d_srs, srs_m, _ptr(_g2_limbs(g2s)),
+                                                      _ptr(np.ascontiguousarray(pa, dtype=np.uint64)),
+                                                      _ptr(np.ascontiguousarray(fa, dtype=np.uint64)), pp, npub,
+                                                      _ptr(ints_to_limbs(chal)), _ptr(ints_to_limbs([u])),
+                                                      _ptr(ints_to_limbs(k1k2)), mode, ctypes.byref(ok), stream))
+        return ok.value == 1
+
+    def plonk_verify_bn254_batch_pi(self, q, copies, srs, g2s, proofs, pubs, chals, us, rhos, k1k2=(2, 3), mode=0,
+                                    each=False):
+        """plonk_verify_bn254_batch over proofs of one circuit with a statement each: pubs[i] the
+        public inputs of proofs[i]."""
+        n = len(q[0])
+        qa = ints_to_limbs([x for col in q for x in col])
+        ca = np.array([v for col in copies for (k, i) in col for v in (k, i)], dtype=np.uint64)
+        sa = _g1_limbs(srs)
+        count, pa, fa, cha, ua, ra = self._batch_arrays(proofs, chals, us, rhos)
+        if len(pubs) != count:
+            raise ValueError("one list of public inputs per proof")
+        pb, npub = self._batch_pub(pubs)
+        ok = ctypes.c_int(-1)
+        oe = (ctypes.c_int * max(count, 1))() if each else None
+        _check(self.lib.pbf_plonk_verify_bn254_batch_pi(self.h, n, _ptr(qa), _ptr(ca), _ptr(sa), len(srs),
+                                                        _ptr(_g2_limbs(g2s)), count, _ptr(pa), _ptr(fa),
+                                                        _ptr(pb) if npub else None, npub, _ptr(cha), _ptr(ua),
+                                                        _ptr(ra), _ptr(ints_to_limbs(k1k2)), mode, ctypes.byref(ok),
+                                                        oe))
+        return (ok.value == 1, [bool(v) for v in oe[:count]]) if each else ok.value == 1
+
+    def plonk_verify_bn254_batch_pi_dev(self, n, d_q, d_copies, d_srs, srs_m, g2s, proofs, pubs, chals, us, rhos,
+                                        k1k2=(2, 3), mode=0, each=False, stream: int = 0):
+        """The same with the circuit and SRS on the device."""
+        count, pa, fa, cha, ua, ra = self._batch_arrays(proofs, chals, us, rhos)
+        if len(pubs) != count:
+            raise ValueError("one list of public inputs per proof")
+        pb, npub = self._batch_pub(pubs)
+        ok = ctypes.c_int(-1)
+        oe = (ctypes.c_int * max(count, 1))() if each else None
+        _check(self.lib.pbf_plonk_verify_bn254_batch_pi_dev(self.h, n, d_q, d_copies, d_srs, srs_m,
+                                                            _ptr(_g2_limbs(g2s)), count, _ptr(pa), _ptr(fa),
+                                                            _ptr(pb) if npub else None, npub, _ptr(cha), _ptr(ua),
+                                                            _ptr(ra), _ptr(ints_to_limbs(k1k2)), mode,
+                                                            ctypes.byref(ok), oe, stream))
         return (ok.value == 1, [bool(v) for v in oe[:count]]) if each else ok.value == 1
 
     # ---- KZG commitments over BN254 (include/pbf.h "KZG commitments"; kzg.hip)
