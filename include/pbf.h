@@ -464,6 +464,71 @@ int pbf_kzg_open_bn254_dev(pbf_ctx* ctx, const uint64_t* d_srs, size_t srs_m, co
 int pbf_kzg_verify_bn254(pbf_ctx* ctx, const uint64_t* g2, size_t count, const uint64_t* commits, const uint64_t* z,
                          const uint64_t* y, const uint64_t* w, const uint64_t* rho, int* ok);
 
+/* ---- Multi-point KZG openings: many polynomials, many points, two G1 points -------------------
+ * The multi-point opening of Boneh, Drake, Fisch and Gabizon ("Efficient polynomial commitment
+ * schemes for multiple points and polynomials", 2020, section 4): `batch` polynomials p_b, each
+ * opened on its own non-empty subset S_b of a set T of npts distinct points, are proven by two G1
+ * points, W and W', with two MSMs on the prover's side however many points there are, and checked
+ * with [s]G2 and one pairing check. srs, srs_m, polys, len, pitch, batch, the elements, the streams
+ * and the results are those of "KZG commitments" above (_dev: device srs and polynomials,
+ * everything else on the host).
+ *   pts    npts x 4 u64, the points t_0 .. t_(npts-1) of T, canonical and distinct, 1 <= npts <= 32
+ *   sets   batch u64 masks: bit j of sets[b] says t_j in S_b; no mask is zero or has a bit at npts
+ *          or above
+ *   gamma, z   the two challenges, one canonical value each. The library derives no challenge:
+ *          gamma must be derived AFTER the commitments and the evaluations y, and z AFTER W (e.g.
+ *          by hashing them into the caller's transcript); soundness rests on that order.
+ * With r_b the interpolation of p_b on S_b and Z_S(x) = prod_{t in S} (x - t):
+ * pbf_kzg_open_multi_bn254*: phase 1.
+ *     out_y[b][j] = p_b(t_j) for j in S_b, zero words elsewhere (batch x npts x 4),
+ *     out_w = W = commit( sum_b gamma^b (p_b - r_b) / Z_{S_b} ).
+ *   The polynomials are grouped by equal set, one weighted sum and one division by Z_S per
+ *   distinct set; the division is |S| synthetic divisions over one read of the sum (partial
+ *   fractions), so there is no failing case and none is added: points may be 0, roots of a
+ *   polynomial or points of an NTT domain, gamma may be 0 (0^0 = 1). Needs srs_m >= len - 1; with
+ *   len = 1 W is the identity and the SRS is not read.
+ * pbf_kzg_open_multi_finish_bn254*: phase 2, after the caller has derived z from W.
+ *     out_w2 = W' = commit( (sum_b gamma^b Z_{T \ S_b}(z) (p_b - r_b(z)) - Z_T(z) h) / (x - z) ),
+ *   h the polynomial W commits to. The call is stateless: it takes the same polynomials, points,
+ *   sets and gamma again and recomputes h (two more sweeps, no MSM). z may be any canonical value,
+ *   a point of T and 0 included. Needs srs_m >= len - 1; with len = 1 W' is the identity.
+ * pbf_kzg_verify_multi_bn254: `count` multi-openings of one shape (batch, npts, sets), each with
+ *   its own commits (count x batch x 8), pts (count x npts x 4), y (count x batch x npts x 4; entries
+ *   outside a set are not read), gamma, z, rho (count x 4 each), w, w2 (count x 8 each); host pointers.
+ *     F_i = sum_b gamma_i^b Z_{T \ S_b}(z_i) (C_ib - r_ib(z_i) G) - Z_T(z_i) W_i
+ *     *ok = [ e(sum_i rho_i W'_i, [s]G2) * e(-sum_i rho_i (F_i + z_i W'_i), G2) == 1 ]
+ *   as one MSM over count points, one over count (batch + 2) + 1 points and one pairing check.
+ *   r_ib(z_i) is taken in product form; nothing is divided by z_i - t_j, so z_i in T is accepted.
+ *   Randomness: the library reads none (the contract of pbf_kzg_verify_bn254). Soundness of the
+ *   batch rests on the caller choosing the weights rho unpredictably and AFTER seeing the openings
+ *   (e.g. by hashing all of them); with predictable or equal weights the errors of two bad
+ *   openings can cancel and the batch passes. count = 1, rho = 1 is the single check.
+ *   A point that is not canonical or not on the curve gives *ok = 0 outright ((0,0) is accepted);
+ *   there is no per-opening localisation.
+ * Errors (PBF_EINVAL, before anything is enqueued or written; never an abort): every error of
+ * pbf_kzg_open_bn254*; npts = 0 or npts > 32; two equal points in pts (per opening in the
+ * verifier); a mask that is zero or has a bit at npts or above; pts, gamma, z or a y inside its
+ * set >= r; rho_i = 0 or >= r; count = 0; count * batch > 2^20.                                 */
+int pbf_kzg_open_multi_bn254(pbf_ctx* ctx, const uint64_t* srs, size_t srs_m, const uint64_t* polys, size_t len,
+                             size_t pitch, size_t batch, const uint64_t* pts, size_t npts, const uint64_t* sets,
+                             const uint64_t* gamma, uint64_t* out_y, uint64_t* out_w);
+int pbf_kzg_open_multi_bn254_dev(pbf_ctx* ctx, const uint64_t* d_srs, size_t srs_m, const uint64_t* d_polys,
+                                 size_t len, size_t pitch, size_t batch, const uint64_t* pts, size_t npts,
+                                 const uint64_t* sets, const uint64_t* gamma, uint64_t* out_y, uint64_t* out_w,
+                                 void* stream);
+int pbf_kzg_open_multi_finish_bn254(pbf_ctx* ctx, const uint64_t* srs, size_t srs_m, const uint64_t* polys, size_t len,
+                                    size_t pitch, size_t batch, const uint64_t* pts, size_t npts,
+                                    const uint64_t* sets, const uint64_t* gamma, const uint64_t* z,
+                                    uint64_t* out_w2);
+int pbf_kzg_open_multi_finish_bn254_dev(pbf_ctx* ctx, const uint64_t* d_srs, size_t srs_m, const uint64_t* d_polys,
+                                        size_t len, size_t pitch, size_t batch, const uint64_t* pts, size_t npts,
+                                        const uint64_t* sets, const uint64_t* gamma, const uint64_t* z,
+                                        uint64_t* out_w2, void* stream);
+int pbf_kzg_verify_multi_bn254(pbf_ctx* ctx, const uint64_t* g2, size_t count, size_t batch, size_t npts,
+                               const uint64_t* sets, const uint64_t* commits, const uint64_t* pts, const uint64_t* y,
+                               const uint64_t* gamma, const uint64_t* z, const uint64_t* w, const uint64_t* w2,
+                               const uint64_t* rho, int* ok);
+
 /* ---- KZG in evaluation form: G1 NTT, Lagrange-basis SRS, opening from evaluations -----------
  * A polynomial of degree < n given by its values on H = <omega> (evals[i] = p(omega^i), as the
  * NTT entry points leave witness columns, extensions and quotients) is committed and opened as it

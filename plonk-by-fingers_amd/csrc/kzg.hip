@@ -85,6 +85,12 @@ __global__ void __launch_bounds__(256) k_kzg_vsum(const uint64_t* part, uint32_t
 
 }  // namespace
 
+int pbf::kzg_vsum_run(const uint64_t* part, uint32_t nparts, uint64_t* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_kzg_vsum, dim3(1), dim3(256), 0, s, part, nparts, out);
+  PBF_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---------------------------------------------------------------- Poly::eval over Fr
 extern "C" int pbf_poly_eval_fr256(pbf_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64_t* xs, size_t nx,
                                    uint64_t* ys) {
@@ -216,7 +222,7 @@ extern "C" int pbf_kzg_verify_bn254(pbf_ctx* ctx, const uint64_t* g2, size_t cou
   hipLaunchKernelGGL(k_kzg_vprep, dim3(nparts), dim3(256), 0, s, (const uint64_t*)v.in, (const uint64_t*)(v.in + 8 * c),
                      (const uint64_t*)d_z, (const uint64_t*)d_y, (const uint64_t*)d_rho, (uint32_t)c, v.pts, v.sc, v.part,
                      v.flag);
-  hipLaunchKernelGGL(k_kzg_vsum, dim3(1), dim3(256), 0, s, (const uint64_t*)v.part, nparts, v.sc + 8 * c);
+  if ((rc = kzg_vsum_run(v.part, nparts, v.sc + 8 * c, s))) return rc;
   // e(sum rho W, [s]G2) e(-sum rho (C - y G + z W), G2) == 1
   return kzg_verify_tail(ctx, v, c, 1, g2, ok, s);
 }

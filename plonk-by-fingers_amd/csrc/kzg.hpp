@@ -1,5 +1,6 @@
-// What the KZG units share (kzg.hip, kzg_evals.hip, kzg_cells.hip, kzg_recover.hip): one statement
-// of every step that more than one scheme takes, inline; only cells_ystore_run crosses units.
+// What the KZG units share (kzg.hip, kzg_multi.hip, kzg_evals.hip, kzg_cells.hip, kzg_recover.hip):
+// one statement of every step that more than one scheme takes, inline; only cells_ystore_run and
+// kzg_vsum_run cross units.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -47,10 +48,10 @@ inline int upload_polys(pbf_ctx* ctx, const uint64_t* srs, size_t srs_m, const u
 }
 
 // ---------------------------------------------------------------- the weighted sum of a batch
-// comb = sum_b c_b p_b on len coefficients, p_b at d_polys + 4 b pitch (c: Montgomery form): 10
-// inputs per launch, later launches taking the sum so far as one of them
-inline int kzg_comb(const uint64_t* d_polys, uint64_t len, uint64_t pitch, uint64_t batch, const U256* c,
-                    uint64_t* comb, hipStream_t s) {
+// comb = sum_b c_b p_b on len coefficients over the `batch` polynomials p_b = poly(b) (c: Montgomery
+// form): 10 inputs per launch, later launches taking the sum so far as one of them
+template <class PolyAt>
+inline int kzg_comb_of(PolyAt poly, uint64_t len, uint64_t batch, const U256* c, uint64_t* comb, hipStream_t s) {
   int rc;
   for (uint64_t b0 = 0; b0 < batch;) {
     const uint64_t* in[10];
@@ -62,12 +63,17 @@ inline int kzg_comb(const uint64_t* d_polys, uint64_t len, uint64_t pitch, uint6
       ck[k++] = fr_one_m();
     }
     while (k < 10 && b0 < batch) {
-      in[k] = d_polys + 4 * b0 * pitch;
+      in[k] = poly(b0);
       ck[k++] = c[b0++];
     }
     if ((rc = fr_lincomb_run(k, in, lens, ck, u256_zero(), comb, len, s))) return rc;
   }
   return 0;
+}
+// the same over a whole batch, p_b at d_polys + 4 b pitch
+inline int kzg_comb(const uint64_t* d_polys, uint64_t len, uint64_t pitch, uint64_t batch, const U256* c,
+                    uint64_t* comb, hipStream_t s) {
+  return kzg_comb_of([=](uint64_t b) { return d_polys + 4 * b * pitch; }, len, batch, c, comb, s);
 }
 
 // ---------------------------------------------------------------- geometry of the cells
@@ -99,9 +105,14 @@ __device__ __forceinline__ U256 fr_domain_pow(const uint64_t* tw, uint64_t n, ui
 // out[(b k + i) l + t] = y[b n + i + k t] for `batch` transforms of size n = k l (k_cells_ystore)
 int cells_ystore_run(const uint64_t* y, uint64_t batch, uint64_t k, uint32_t log_l, uint64_t* out, hipStream_t s);
 
+// kzg.hip: *out = -(sum of the nparts partial sums at part), the scalar of G of the verifiers of
+// kzg.hip and kzg_multi.hip (k_kzg_vsum)
+int kzg_vsum_run(const uint64_t* part, uint32_t nparts, uint64_t* out, hipStream_t s);
+
 // ---------------------------------------------------------------- the batched verifiers
-// Both check e(sum rho_i W_i, g2[1]) e(-(sum of sc pts), g2[0]) == 1 on the context's kzg.v.*
-// buffers, pts = [C_0.. | W_0.. | `extra` shared bases], and differ in the scalars sc only.
+// All check e(sum rho_i W_i, g2[1]) e(-(sum of sc pts), g2[0]) == 1 on the context's kzg.v.*
+// buffers. The single-point ones keep pts = [C_0.. | W_0.. | `extra` shared bases] and differ in
+// the scalars sc only; the multi-point one has more points per opening and says where its W are.
 struct KzgVerify {
   uint64_t *in, *pts, *sc, *part;
   int* flag;
@@ -146,23 +157,29 @@ __device__ __forceinline__ void kzg_vpoints(const uint64_t* commits, const uint6
   }
 }
 // After the scheme's kernels: a flagged point gives *ok = 0 (set by the caller) and PBF_OK; else
-// the MSM over the W half, the MSM over all 2 c + extra points, one pairing check.
-inline int kzg_verify_tail(pbf_ctx* ctx, const KzgVerify& v, size_t c, size_t extra, const uint64_t* g2, int* ok,
-                           hipStream_t s) {
+// the MSM over the c points w_pts with the scalars w_sc (sum rho_i W_i), the MSM over all `total`
+// points of v.pts with v.sc, one pairing check.
+inline int kzg_verify_tail_at(pbf_ctx* ctx, const KzgVerify& v, const uint64_t* w_pts, const uint64_t* w_sc, size_t c,
+                              size_t total, const uint64_t* g2, int* ok, hipStream_t s) {
   PBF_HIP(hipGetLastError());
   int bad = 0, rc;
   PBF_HIP(hipMemcpyAsync(&bad, v.flag, sizeof(int), hipMemcpyDeviceToHost, s));
   PBF_HIP(hipStreamSynchronize(s));
   if (bad) return PBF_OK;
   uint64_t e1[8], e2[8];
-  if ((rc = pbf_msm_g1_bn254_dev(ctx, v.pts + 8 * c, v.sc, c, e1, s))) return rc;  // sum rho_i W_i
-  if ((rc = pbf_msm_g1_bn254_dev(ctx, v.pts, v.sc, 2 * c + extra, e2, s))) return rc;
+  if ((rc = pbf_msm_g1_bn254_dev(ctx, w_pts, w_sc, c, e1, s))) return rc;  // sum rho_i W_i
+  if ((rc = pbf_msm_g1_bn254_dev(ctx, v.pts, v.sc, total, e2, s))) return rc;
   uint64_t g1s[16], g2s[32];
   memcpy(g1s, e1, 64);
   neg_g1(e2, g1s + 8);
   memcpy(g2s, g2 + 16, 128);  // [s]G2, or [s^l]G2 for cells
   memcpy(g2s + 16, g2, 128);  // G2
   return pairing_check_on_stream(ctx, g1s, g2s, 2, ok, s);
+}
+// the layout [C | W | extra]: the W half carries rho at the head of sc
+inline int kzg_verify_tail(pbf_ctx* ctx, const KzgVerify& v, size_t c, size_t extra, const uint64_t* g2, int* ok,
+                           hipStream_t s) {
+  return kzg_verify_tail_at(ctx, v, v.pts + 8 * c, v.sc, c, 2 * c + extra, g2, ok, s);
 }
 
 }  // namespace pbf

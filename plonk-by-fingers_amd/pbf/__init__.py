@@ -140,6 +140,16 @@ SIGNATURES = [
     ("pbf_kzg_open_bn254_dev", ctypes.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _p64, _p64, _p64, _p64, _vp]),
     ("pbf_kzg_verify_bn254", ctypes.c_int, [_vp, _p64, _sz, _p64, _p64, _p64, _p64, _p64,
                                             ctypes.POINTER(ctypes.c_int)]),
+    ("pbf_kzg_open_multi_bn254", ctypes.c_int, [_vp, _p64, _sz, _p64, _sz, _sz, _sz, _p64, _sz, _p64, _p64, _p64,
+                                                _p64]),
+    ("pbf_kzg_open_multi_bn254_dev", ctypes.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _p64, _sz, _p64, _p64, _p64,
+                                                    _p64, _vp]),
+    ("pbf_kzg_open_multi_finish_bn254", ctypes.c_int, [_vp, _p64, _sz, _p64, _sz, _sz, _sz, _p64, _sz, _p64, _p64,
+                                                       _p64, _p64]),
+    ("pbf_kzg_open_multi_finish_bn254_dev", ctypes.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _p64, _sz, _p64, _p64,
+                                                           _p64, _p64, _vp]),
+    ("pbf_kzg_verify_multi_bn254", ctypes.c_int, [_vp, _p64, _sz, _sz, _sz, _p64, _p64, _p64, _p64, _p64, _p64, _p64,
+                                                  _p64, _p64, ctypes.POINTER(ctypes.c_int)]),
     ("pbf_ntt_g1_bn254", ctypes.c_int, [_vp, _p64, _p64, _p64, _sz, ctypes.c_int]),
     ("pbf_ntt_g1_bn254_dev", ctypes.c_int, [_vp, _p64, _vp, _vp, _sz, ctypes.c_int, _vp]),
     ("pbf_ntt_g1_bn254_batch", ctypes.c_int, [_vp, _p64, _p64, _p64, _sz, _sz, ctypes.c_int]),
@@ -729,6 +739,84 @@ class Context:
                                              _ptr(ints_to_limbs([e[2] for e in entries])),
                                              _ptr(_g1_limbs([e[3] for e in entries])),
                                              _ptr(ints_to_limbs(list(rhos))), ctypes.byref(ok)))
+        return ok.value == 1
+
+    # ---- multi-point openings (include/pbf.h "Multi-point KZG openings"; kzg_multi.hip)
+    @staticmethod
+    def _sets(sets) -> np.ndarray:
+        return np.array([int(m) for m in sets], dtype=np.uint64)
+
+    def _multi_ys(self, ys, batch, npts) -> list:
+        v = limbs_to_ints(ys)
+        return [v[b * npts:(b + 1) * npts] for b in range(batch)]
+
+    def kzg_open_multi(self, srs, polys, pts, sets, gamma: int, pitch: int | None = None):
+        """pbf_kzg_open_multi_bn254, phase 1 of the multi-point opening: polynomial b is opened on
+        the points t_j of pts whose bit j is set in sets[b]. (ys, W): ys[b][j] = p_b(t_j) inside
+        the set and 0 outside. gamma is the caller's challenge, derived after the commitments and
+        the evaluations (include/pbf.h)."""
+        a, ln, pitch, batch = self._poly_limbs(polys, pitch)
+        npts = len(pts)
+        ys = np.zeros(4 * max(batch * npts, 1), dtype=np.uint64)
+        w = np.zeros(8, dtype=np.uint64)
+        _check(self.lib.pbf_kzg_open_multi_bn254(self.h, _ptr(_g1_limbs(srs) if len(srs) else np.zeros(8, np.uint64)),
+                                                 len(srs), _ptr(a), ln, pitch, batch,
+                                                 _ptr(ints_to_limbs(list(pts))), npts, _ptr(self._sets(sets)),
+                                                 _ptr(ints_to_limbs([gamma])), _ptr(ys), _ptr(w)))
+        return self._multi_ys(ys, batch, npts), self._points(w)[0]
+
+    def kzg_open_multi_dev(self, d_srs: int, srs_m: int, d_polys: int, length: int, pitch: int, batch: int, pts, sets,
+                           gamma: int, stream: int = 0):
+        npts = len(pts)
+        ys = np.zeros(4 * max(batch * npts, 1), dtype=np.uint64)
+        w = np.zeros(8, dtype=np.uint64)
+        _check(self.lib.pbf_kzg_open_multi_bn254_dev(self.h, _vp(d_srs), srs_m, _vp(d_polys), length, pitch, batch,
+                                                     _ptr(ints_to_limbs(list(pts))), npts, _ptr(self._sets(sets)),
+                                                     _ptr(ints_to_limbs([gamma])), _ptr(ys), _ptr(w),
+                                                     _vp(stream) if stream else None))
+        return self._multi_ys(ys, batch, npts), self._points(w)[0]
+
+    def kzg_open_multi_finish(self, srs, polys, pts, sets, gamma: int, z: int, pitch: int | None = None):
+        """pbf_kzg_open_multi_finish_bn254, phase 2: W' for the challenge z, which the caller derives
+        after W. Stateless: the arguments of kzg_open_multi again, and z."""
+        a, ln, pitch, batch = self._poly_limbs(polys, pitch)
+        w2 = np.zeros(8, dtype=np.uint64)
+        _check(self.lib.pbf_kzg_open_multi_finish_bn254(
+            self.h, _ptr(_g1_limbs(srs) if len(srs) else np.zeros(8, np.uint64)), len(srs), _ptr(a), ln, pitch, batch,
+            _ptr(ints_to_limbs(list(pts))), len(pts), _ptr(self._sets(sets)), _ptr(ints_to_limbs([gamma])),
+            _ptr(ints_to_limbs([z])), _ptr(w2)))
+        return self._points(w2)[0]
+
+    def kzg_open_multi_finish_dev(self, d_srs: int, srs_m: int, d_polys: int, length: int, pitch: int, batch: int, pts,
+                                  sets, gamma: int, z: int, stream: int = 0):
+        w2 = np.zeros(8, dtype=np.uint64)
+        _check(self.lib.pbf_kzg_open_multi_finish_bn254_dev(
+            self.h, _vp(d_srs), srs_m, _vp(d_polys), length, pitch, batch, _ptr(ints_to_limbs(list(pts))), len(pts),
+            _ptr(self._sets(sets)), _ptr(ints_to_limbs([gamma])), _ptr(ints_to_limbs([z])), _ptr(w2),
+            _vp(stream) if stream else None))
+        return self._points(w2)[0]
+
+    def kzg_verify_multi(self, g2s, sets, openings, rhos) -> bool:
+        """pbf_kzg_verify_multi_bn254: openings of one shape, each (commits, pts, ys, gamma, z, W, W')
+        with ys[b][j] as kzg_open_multi returns it (entries outside a set are not read); rhos the
+        batching weights: nonzero, < r, chosen unpredictably after seeing the openings (soundness
+        rests on that; include/pbf.h). One pairing check whatever the count."""
+        if len(openings) != len(rhos):
+            raise ValueError("one rho per opening")
+        batch = len(sets)
+        npts = len(openings[0][1]) if openings else 0
+        if any(len(o[0]) != batch or len(o[1]) != npts or len(o[2]) != batch or any(len(r) != npts for r in o[2])
+               for o in openings):
+            raise ValueError("the openings of one call have one shape")
+        ok = ctypes.c_int(-1)
+        _check(self.lib.pbf_kzg_verify_multi_bn254(
+            self.h, _ptr(_g2_limbs(g2s)), len(openings), batch, npts, _ptr(self._sets(sets)),
+            _ptr(_g1_limbs([c for o in openings for c in o[0]])),
+            _ptr(ints_to_limbs([t for o in openings for t in o[1]])),
+            _ptr(ints_to_limbs([v for o in openings for r in o[2] for v in r])),
+            _ptr(ints_to_limbs([o[3] for o in openings])), _ptr(ints_to_limbs([o[4] for o in openings])),
+            _ptr(_g1_limbs([o[5] for o in openings])), _ptr(_g1_limbs([o[6] for o in openings])),
+            _ptr(ints_to_limbs(list(rhos))), ctypes.byref(ok)))
         return ok.value == 1
 
     # ---- KZG in evaluation form (include/pbf.h "KZG in evaluation form"; g1_ntt.hip, kzg_evals.hip)
