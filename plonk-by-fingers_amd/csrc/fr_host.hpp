@@ -1,7 +1,8 @@
 // One copy of the small BN254 helpers every unit's host code needs: Fr values in and out of
 // Montgomery form, powers and the Fermat inverse, the root of unity, the canonical test, and the
-// two G1 checks of the verifiers. fr_one_m, fr_pow and fr_inv are also what the prover's kernels
-// call. Everything takes and returns Montgomery form unless it says canonical.
+// two G1 checks of the verifiers. fr_one_m, fr_pow, fr_inv and hout are also what kernels call
+// (the prover's, the batched verifier's). Everything takes and returns Montgomery form unless it
+// says canonical.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -31,6 +32,8 @@ __host__ __device__ inline U256 fr_inv(const U256& a) {
   }
   return r;
 }
+// out of Montgomery form, to 4 little-endian u64 limbs (canonical)
+__host__ __device__ __forceinline__ void hout(uint64_t* p, const U256& m) { u256_to_u64(Fr::from_mont(m), p); }
 
 // ---------------------------------------------------------------- host only
 // 4 little-endian u64 limbs (any 256-bit value, reduced mod r) / a u64, to Montgomery form
@@ -49,7 +52,6 @@ inline U256 hpowm(U256 a, const U256& e_plain) {  // exponent given as plain U25
   }
   return r;
 }
-inline void hout(uint64_t* p, const U256& m) { u256_to_u64(Fr::from_mont(m), p); }
 inline bool heq1(const U256& m) { return Fr::eq(m, fr_one_m()); }
 // primitive 2^k-th root of unity of Fr: 5^((r-1)/2^k)
 inline U256 fr_root_of_unity(uint32_t log_n) {

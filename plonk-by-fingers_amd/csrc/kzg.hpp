@@ -169,12 +169,7 @@ inline int kzg_verify_tail_at(pbf_ctx* ctx, const KzgVerify& v, const uint64_t* 
   uint64_t e1[8], e2[8];
   if ((rc = pbf_msm_g1_bn254_dev(ctx, w_pts, w_sc, c, e1, s))) return rc;  // sum rho_i W_i
   if ((rc = pbf_msm_g1_bn254_dev(ctx, v.pts, v.sc, total, e2, s))) return rc;
-  uint64_t g1s[16], g2s[32];
-  memcpy(g1s, e1, 64);
-  neg_g1(e2, g1s + 8);
-  memcpy(g2s, g2 + 16, 128);  // [s]G2, or [s^l]G2 for cells
-  memcpy(g2s + 16, g2, 128);  // G2
-  return pairing_check_on_stream(ctx, g1s, g2s, 2, ok, s);
+  return pairing_tail(ctx, e1, e2, g2, ok, s);  // g2[1]: [s]G2, or [s^l]G2 for cells
 }
 // the layout [C | W | extra]: the W half carries rho at the head of sc
 inline int kzg_verify_tail(pbf_ctx* ctx, const KzgVerify& v, size_t c, size_t extra, const uint64_t* g2, int* ok,

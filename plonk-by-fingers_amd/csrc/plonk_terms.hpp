@@ -1,7 +1,11 @@
-// The scalar terms of Plonk::prove's rounds 4 and 5 (src/plonk.rs:401-439), stated once for the
-// one-GPU and the sharded prover (prover.hip): the coefficients of the linearisation r(x) and of
-// the W_z numerator as linear combinations of polynomials. Host only, every value in Montgomery
-// form; each prover binds its own pointers and lengths to the coefficients.
+// The scalar terms of the protocol, each stated once for the code paths that need it. Every value
+// is in Montgomery form.
+//   Plonk::prove's rounds 4 and 5 (src/plonk.rs:401-439), for the one-GPU and the sharded prover
+//   (prover.hip): the coefficients of the linearisation r(x) and of the W_z numerator as linear
+//   combinations of polynomials; each prover binds its own pointers and lengths to them. Host only.
+//   Plonk::verify's steps 4-10 (src/plonk.rs:549-634), for the single verifier on the host
+//   (verify.hip) and the batched one on the device (verify_batch.hip k_vb_scalars): the 18 MSM
+//   scalars and the 2 of E1 from a proof's evaluations and challenges. Host and device.
 #pragma once
 #include "fr_host.hpp"
 
@@ -60,6 +64,140 @@ inline U256 plonk_wz_coeffs(const PlonkChallenges& ch, const PlonkEvals& e, uint
   cst = Fr::add(cst, Fr::mul(vp[5], e.s1_z));
   cst = Fr::add(cst, Fr::mul(vp[6], e.s2_z));
   return Fr::sub(U256{}, cst);
+}
+
+// ---------------------------------------------------------------- Plonk::verify steps 4-10
+// The Fr product as a call: the verifier's scalars are ~120 products of straight line, and the
+// device keeps one copy of the product's code per kernel.
+__host__ __device__ __noinline__ inline U256 fmul(U256 a, U256 b) { return Fr::mul(a, b); }
+// a^(r-2): Fermat inverse (a != 0) over fmul
+__host__ __device__ inline U256 fmul_inv(const U256& a, const U256& one) {
+  U256 r = one;
+#pragma unroll 1
+  for (int i = 255; i >= 0; --i) {
+    r = fmul(r, r);
+    const uint32_t e = Bn254FrParams::P[i / 32] - (i < 32 ? 2u : 0u);
+    if ((e >> (i % 32)) & 1) r = fmul(r, a);
+  }
+  return r;
+}
+
+// The domain of n = 2^log_n gates: omega = fr_root_of_unity(log_n) of order n, and n^-1
+struct PlonkDomain {
+  uint32_t log_n;
+  U256 omega, n_inv;
+};
+inline PlonkDomain plonk_domain(uint64_t n) {
+  PlonkDomain d{};
+  while (((uint64_t)1 << d.log_n) < n) ++d.log_n;
+  d.omega = fr_root_of_unity(d.log_n);
+  d.n_inv = fr_inv(hm64(n));
+  return d;
+}
+
+// what the verifier's scalars take besides the challenges and the proof: the verifier's random u
+// (plonk.rs:519) and the batching weight rho (1 for a proof on its own)
+struct PlonkVerifierArgs {
+  U256 u, rho;
+  PlonkDomain dom;
+  int mode;
+};
+
+// Steps 4-10 for one proof as the scalars of one linear combination of points, every one times rho.
+// Each is handed to out(j, value) as soon as it is known, j in the order
+//   0 .. 8    on the proof's a b c z t_lo t_mid t_hi w_z w_zw:
+//             rho (v^2, v^3, v^4, d_2, 1, z^(n+2), z^(2n+4), z, u z omega)
+//   9, 10     of E1 = W_z + u W_zw: rho, rho u
+//   11 .. 19  on the shared bases q_m q_l q_r q_o q_c s1 s2 s3 G:
+//             rho (v a_z b_z, v a_z, v b_z, v c_z, v, v^5, v^6, -d_3, -E)
+// so the caller decides where and in which form they are kept, and the device holds none longer
+// than its store takes. e.l1_z and e.t_z are not read: L_1(z) = (z^n - 1) / (n (z - 1)) and step 7's
+// t_z come from here. pi_nd: null, or the public inputs' fraction (N, D) in Montgomery form as
+// plonk_pi_fraction_run stores it (2 x 4 u64), read where it is used:
+// sum_j pub_j w^j / (z - w^j) = N / D, D != 0 for z outside H; step 7 then takes r_z + PI(z),
+// PI(z) = -Z_H(z) n^-1 N / D. mode 0 keeps the reference's step 7 (plonk.rs:575-581, no alpha on
+// the permutation term), mode 1 the paper's.
+// Returns false with no output when Z_H(z) = 0, where the reference's .unwrap() would panic
+// (plonk.rs:581); z = 1 is such a z, so one inversion of Z_H(z) (z - 1) [D] serves every quotient.
+template <class Out>
+__host__ __device__ __forceinline__ bool plonk_verifier_scalars(const PlonkChallenges& ch, const PlonkEvals& e,
+                                                                const PlonkVerifierArgs& g, const uint64_t* pi_nd,
+                                                                Out out) {
+  const U256 one = fr_one_m();
+  const U256 &alpha = ch.alpha, &beta = ch.beta, &gamma = ch.gamma, &zc = ch.z, &v = ch.v, &u = g.u, &rho = g.rho;
+  // Step 4: Z_H(z) = z^n - 1
+  U256 zn = zc;
+#pragma unroll 1
+  for (uint32_t k = 0; k < g.dom.log_n; ++k) zn = fmul(zn, zn);
+  const U256 z_h_z = Fr::sub(zn, one);
+  if (Fr::is_zero(z_h_z)) return false;
+  // Step 5: L_1(z), with 1 / Z_H(z) and 1 / D from the same inversion
+  const U256 zm1 = Fr::sub(zc, one);
+  const U256 zhm = fmul(z_h_z, zm1);
+  U256 tinv, rpi_z = e.r_z;  // r_z + PI(z)
+  if (pi_nd) {
+    const U256 piN = u256_from_u64(pi_nd), piD = u256_from_u64(pi_nd + 4);
+    const U256 all = fmul_inv(fmul(zhm, piD), one);
+    tinv = fmul(all, piD);
+    rpi_z = Fr::sub(e.r_z, fmul(fmul(fmul(z_h_z, g.dom.n_inv), piN), fmul(all, zhm)));
+  } else {
+    tinv = fmul_inv(zhm, one);
+  }
+  const U256 inv_zh = fmul(tinv, zm1);
+  const U256 l1 = fmul(fmul(z_h_z, fmul(tinv, z_h_z)), g.dom.n_inv);
+  // Step 7: t_z
+  const U256 alpha2 = fmul(alpha, alpha);
+  const U256 l1a2 = fmul(l1, alpha2);
+  const U256 pa = Fr::add(Fr::add(e.a_z, fmul(beta, e.s1_z)), gamma);
+  const U256 pb = Fr::add(Fr::add(e.b_z, fmul(beta, e.s2_z)), gamma);
+  const U256 pab = fmul(pa, pb);
+  U256 perm = fmul(pab, fmul(Fr::add(e.c_z, gamma), e.zw_z));
+  if (g.mode == 1) perm = fmul(perm, alpha);
+  const U256 t_z = fmul(Fr::sub(Fr::sub(rpi_z, perm), l1a2), inv_zh);
+  // Steps 8-10
+  U256 vp[7];
+  vp[0] = one;
+  for (int k = 1; k < 7; ++k) vp[k] = fmul(vp[k - 1], v);
+  const U256 bz = fmul(beta, zc);
+  const U256 d2 = Fr::add(
+      Fr::add(fmul(fmul(fmul(fmul(Fr::add(Fr::add(e.a_z, bz), gamma), Fr::add(Fr::add(e.b_z, fmul(bz, ch.k1)), gamma)),
+                             Fr::add(Fr::add(e.c_z, fmul(bz, ch.k2)), gamma)),
+                        alpha),
+                   v),
+              fmul(l1a2, v)),
+      u);
+  const U256 d3 = fmul(fmul(fmul(fmul(pab, alpha), v), beta), e.zw_z);
+  U256 ecoef = Fr::add(t_z, fmul(v, e.r_z));
+  ecoef = Fr::add(ecoef, fmul(vp[2], e.a_z));
+  ecoef = Fr::add(ecoef, fmul(vp[3], e.b_z));
+  ecoef = Fr::add(ecoef, fmul(vp[4], e.c_z));
+  ecoef = Fr::add(ecoef, fmul(vp[5], e.s1_z));
+  ecoef = Fr::add(ecoef, fmul(vp[6], e.s2_z));
+  ecoef = Fr::add(ecoef, fmul(u, e.zw_z));
+  const U256 zn2 = fmul(zn, fmul(zc, zc));  // z^(n+2)
+  out(0, fmul(rho, vp[2]));                   // a_s
+  out(1, fmul(rho, vp[3]));                   // b_s
+  out(2, fmul(rho, vp[4]));                   // c_s
+  out(3, fmul(rho, d2));                      // z_s
+  out(4, rho);                                // t_lo
+  out(5, fmul(rho, zn2));                     // t_mid
+  out(6, fmul(rho, fmul(zn2, zn2)));          // t_hi: z^(2n+4)
+  out(7, fmul(rho, zc));                      // w_z * z
+  const U256 ru = fmul(rho, u);
+  out(8, fmul(ru, fmul(zc, g.dom.omega)));        // w_zw * u z w
+  out(9, rho);
+  out(10, ru);
+  const U256 rv = fmul(rho, v);
+  out(11, fmul(rv, fmul(e.a_z, e.b_z)));      // q_m
+  out(12, fmul(rv, e.a_z));                   // q_l
+  out(13, fmul(rv, e.b_z));                   // q_r
+  out(14, fmul(rv, e.c_z));                   // q_o
+  out(15, rv);                                // q_c
+  out(16, fmul(rho, vp[5]));                  // s1
+  out(17, fmul(rho, vp[6]));                  // s2
+  out(18, Fr::sub(U256{}, fmul(rho, d3)));    // - s3 d3
+  out(19, Fr::sub(U256{}, fmul(rho, ecoef))); // - E
+  return true;
 }
 
 }  // namespace pbf

@@ -4,6 +4,8 @@
 // sigma labels). Plonk::prove goes through the same launchers. Then what g1_ntt.hip, g1_mul.hip
 // and verify.hip export to the same users, and two device helpers over Fr.
 #pragma once
+#include <cstring>
+#include <initializer_list>
 #include "fr_host.hpp"
 #include "msm.hpp"
 
@@ -110,12 +112,49 @@ int g1_ntt_run(pbf_ctx* ctx, const U256& wm, const uint64_t* d_in, uint64_t* d_o
 int g1_mul_xyzz_run(const G1Work& w, const uint64_t* d_points, const uint64_t* d_scalars, uint64_t n, uint64_t batch,
                     hipStream_t s);
 
-// verify.hip: Plonk::verify's preprocessing, shared by the single and the batched verifier:
+// verify.hip, then what the single and the batched verifier (and, for pairing_tail, the KZG
+// ones) state once, inline. Plonk::verify's preprocessing, shared by the single and the batched verifier:
 // pre = the commitments of q_m q_l q_r q_o q_c s_sigma_1..3 (canonical affine), from the
 // context's verification key when option verifier.vk allows and q, copies and the SRS equal
 // their snapshots, else recomputed. omega = fr_root_of_unity(log2 n), Montgomery form.
 int verifier_vk(pbf_ctx* ctx, size_t n, const U256& omega, const uint64_t* d_q, const uint64_t* d_copies,
                 const uint64_t* d_srs, size_t srs_m, const uint64_t* k1k2, hipStream_t s, uint64_t pre[8][8]);
+// The argument errors both verifiers share, before anything is enqueued: a null among ptrs or ok,
+// then (with *ok zeroed) n not a power of two >= 8, then an SRS shorter than n.
+inline int verifier_shape(std::initializer_list<const void*> ptrs, size_t n, size_t srs_m, int* ok) {
+  for (const void* p : ptrs)
+    if (!p) return fail(PBF_EINVAL, "null argument");
+  if (!ok) return fail(PBF_EINVAL, "null argument");
+  *ok = 0;
+  if (n < 8 || (n & (n - 1))) return fail(PBF_EINVAL, "n must be a power of two >= 8");
+  if (srs_m < n) return fail(PBF_EINVAL, "SRS too short");
+  return 0;
+}
+// The host forms' circuit and SRS on the device (the context's vf.q, vf.copies, vf.srs), enqueued on s
+inline int verifier_upload(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies, const uint64_t* srs,
+                           size_t srs_m, hipStream_t s, const uint64_t** d_q, const uint64_t** d_copies,
+                           const uint64_t** d_srs) {
+  DevBuf &dq = ctx->buf("vf.q"), &dc = ctx->buf("vf.copies"), &dsrs = ctx->buf("vf.srs");
+  int rc;
+  if ((rc = dq.ensure(5 * n * 32)) || (rc = dc.ensure(3 * n * 16)) || (rc = dsrs.ensure(srs_m * 64))) return rc;
+  PBF_HIP(hipMemcpyAsync(dq.p, q, 5 * n * 32, hipMemcpyHostToDevice, s));
+  PBF_HIP(hipMemcpyAsync(dc.p, copies, 3 * n * 16, hipMemcpyHostToDevice, s));
+  PBF_HIP(hipMemcpyAsync(dsrs.p, srs, srs_m * 64, hipMemcpyHostToDevice, s));
+  *d_q = (const uint64_t*)dq.p, *d_copies = (const uint64_t*)dc.p, *d_srs = (const uint64_t*)dsrs.p;
+  return 0;
+}
+// The last step of every KZG-based verifier: *ok = [e(E1, g2[1]) == e(E2, g2[0])], as the one
+// check e(E1, g2[1]) e(-E2, g2[0]) == 1 (plonk.rs:646-650). e1, e2: affine G1 (8 x u64, host);
+// g2 = [G2, [s]G2] (or [s^l]G2 for cells), 2 x 16 u64, host.
+inline int pairing_tail(pbf_ctx* ctx, const uint64_t* e1, const uint64_t* e2, const uint64_t* g2, int* ok,
+                        hipStream_t s) {
+  uint64_t g1s[16], g2s[32];
+  memcpy(g1s, e1, 64);
+  neg_g1(e2, g1s + 8);
+  memcpy(g2s, g2 + 16, 128);
+  memcpy(g2s + 16, g2, 128);
+  return pairing_check_on_stream(ctx, g1s, g2s, 2, ok, s);
+}
 
 // verify_batch.hip: public inputs of the _pi verifiers. pub (host, count x npub canonical values)
 // against the contract of pbf.h: PBF_EINVAL for npub > n, a null pub with npub > 0, a value >= r.

@@ -13,20 +13,23 @@
 // Work split:
 //   k_vb_curve    one lane per proof POINT: canonical coordinates, y^2 = x^3 + 3 in Fq; ORs
 //                 into the proof's flag; gathers W_z, W_zw into the compact E1 point array
-//   k_vb_scalars  one lane per PROOF (blocks of one wave): fields canonical, Z_H(z) != 0, then
-//                 the single verifier's Fr formulas (steps 4-10) scaled by rho_i; a flagged
+//   k_vb_scalars  one lane per PROOF (blocks of one wave): fields canonical, then steps 4-10 as
+//                 plonk_terms.hpp states them for this kernel and the single verifier
+//                 (plonk_verifier_scalars: Z_H(z) != 0, the Fr formulas scaled by rho_i); a flagged
 //                 proof's scalars are written as zero, so its points ride through the MSM inert
 //   k_vb_pi_*     public inputs (the _pi entries): sum_j pub_ij w^j / (z_i - w^j) of every proof as
 //                 one fraction (N_i, D_i): a wave per (chunk of 256 inputs, proof), then a wave per
-//                 proof over its chunks; k_vb_scalars folds D_i into its one inversion
+//                 proof over its chunks; plonk_verifier_scalars folds D_i into its one inversion
 //   k_vb_colsum*  the 9 shared-base scalars of an index range [lo, hi): LDS tree per block,
 //                 second step across blocks (field addition is exact: any order, same limbs)
-// Every scalar is the canonical value the host formulas give. Localisation (ok_each) halves the
-// index range, recomputing only the column sums, the two MSMs and the pairing per range.
+// Every scalar is the canonical value the single verifier's run of the same formulas gives.
+// Localisation (ok_each) halves the index range, recomputing only the column sums, the two MSMs and
+// the pairing per range.
 #include <algorithm>
 #include <cstring>
 #include <vector>
 #include "../../include/pbf.h"
+#include "plonk_terms.hpp"
 #include "prover.hpp"
 
 using namespace pbf;
@@ -34,33 +37,17 @@ using namespace pbf;
 namespace {
 
 constexpr uint32_t VB_PART = 64;  // column-sum partial blocks per column (one wave in step 2)
-// The E1 MSM runs over W_z, W_zw gathered compactly: E1_N points and scalars per proof, rho and
-// rho u at offset E1_AT.
-constexpr uint32_t E1_N = 2, E1_AT = 0;
+// The E1 MSM runs over W_z, W_zw gathered compactly: E1_N points and scalars (rho, rho u) per proof.
+constexpr uint32_t E1_N = 2;
 
 struct VbParams {
-  U256 k1, k2, omega, n_inv;  // Montgomery
-  uint32_t log_n, count;
+  U256 k1, k2;  // Montgomery
+  PlonkDomain dom;
+  uint32_t count;
   int mode;
 };
 
 __device__ __forceinline__ U256 ldm(const uint64_t* p) { return Fr::to_mont(u256_from_u64(p)); }
-__device__ __forceinline__ void stm(uint64_t* p, const U256& m) { u256_to_u64(Fr::from_mont(m), p); }
-// one copy of the product's code per kernel: the scalar kernel is ~120 products of straight line
-__device__ __noinline__ U256 fmul(U256 a, U256 b) { return Fr::mul(a, b); }
-
-// a^(r-2): Fermat inverse (a != 0)
-__device__ U256 vb_inv(const U256& a, const U256& one) {
-  U256 r = one;
-#pragma unroll 1
-  for (int i = 255; i >= 0; --i) {
-    r = fmul(r, r);
-    const uint32_t e = Bn254FrParams::P[i / 32] - (i < 32 ? 2u : 0u);
-    if ((e >> (i % 32)) & 1) r = fmul(r, a);
-  }
-  return r;
-}
-
 __device__ __forceinline__ void st_zero(uint64_t* p) { p[0] = p[1] = p[2] = p[3] = 0; }
 
 // flag bits: 1 a point not canonical / off the curve, 2 a field >= r, 4 Z_H(z) = 0
@@ -93,12 +80,13 @@ __global__ void __launch_bounds__(256) k_vb_curve(const uint64_t* pts, uint32_t 
   if (bad) atomicOr(flag + i, 1);
 }
 
-// verify.hip steps 4-10 for proof i = one lane, every output times rho_i:
+// Steps 4-10 (plonk_terms.hpp plonk_verifier_scalars) for proof i = one lane, every output times rho_i:
 //   sc[9 i + j]      j < 9: a b c z t_lo t_mid t_hi w_z w_zw
-//   e1s[E1_N i + E1_AT + 0, 1]  rho, rho u
+//   e1s[E1_N i + 0, 1]  rho, rho u
 //   contrib[j][i]    j < 9: q_m q_l q_r q_o q_c s1 s2 (-d3 on s3) (-E on G)
-// PI: step 7 takes r_z + PI(z) with PI(z) = -Z_H(z) n^-1 N_i / D_i from pi_nd (k_vb_pi_*); D_i
-// joins the one inversion (3 products more). PI = false is the kernel of the plain entries.
+// What is about storage stays here: the fields canonical, and zeros for a flagged proof (Z_H(z) is
+// looked at only for a proof not yet flagged). PI: step 7 takes r_z + PI(z) from the fraction
+// (N_i, D_i) of pi_nd (k_vb_pi_*); PI = false is the kernel of the plain entries.
 template <bool PI>
 __global__ void __launch_bounds__(64) k_vb_scalars(const uint64_t* __restrict__ pf, const uint64_t* __restrict__ chal,
                                                    const uint64_t* __restrict__ u_in, const uint64_t* __restrict__ rho_in,
@@ -111,98 +99,27 @@ __global__ void __launch_bounds__(64) k_vb_scalars(const uint64_t* __restrict__ 
   int bad = flag[i];
   for (int k = 0; k < 7; ++k)
     if (Fr::geq_p(u256_from_u64(f + 4 * k))) bad |= 2;
-  const U256 one = Fr::to_mont(Fr::one_plain());
-  const U256 zc = ldm(ch + 12);
-  // Step 4: Z_H(z) = z^n - 1
-  U256 zn = zc;
-#pragma unroll 1
-  for (uint32_t k = 0; k < P.log_n; ++k) zn = fmul(zn, zn);
-  const U256 z_h_z = Fr::sub(zn, one);
-  if (Fr::is_zero(z_h_z)) bad |= 4;
+  if (!bad) {
+    const PlonkChallenges c{ldm(ch), ldm(ch + 4), ldm(ch + 8), ldm(ch + 12), ldm(ch + 16), P.k1, P.k2};
+    PlonkEvals e;  // Proof order: a b c s1 s2 r zw
+    e.a_z = ldm(f), e.b_z = ldm(f + 4), e.c_z = ldm(f + 8), e.s1_z = ldm(f + 12), e.s2_z = ldm(f + 16);
+    e.r_z = ldm(f + 20), e.zw_z = ldm(f + 24);
+    const PlonkVerifierArgs g{ldm(u_in + 4 * (uint64_t)i), ldm(rho_in + 4 * (uint64_t)i), P.dom, P.mode};
+    const uint32_t count = P.count;
+    const auto store = [=](int j, const U256& m) {  // canonical, where the MSMs and the column sums read
+      hout(j < 9 ? sc + 4 * ((uint64_t)9 * i + j)
+                 : j < 11 ? e1s + 4 * ((uint64_t)E1_N * i + (j - 9)) : contrib + 4 * ((uint64_t)(j - 11) * count + i),
+           m);
+    };
+    // D_i = prod_j (z w^-j - 1) is zero only for z in H, which is Z_H(z) = 0: never read then
+    if (!plonk_verifier_scalars(c, e, g, PI ? pi_nd + 8 * (uint64_t)i : nullptr, store)) bad = 4;
+  }
   if (bad) {
     flag[i] = bad;
     for (int j = 0; j < 9; ++j) st_zero(sc + 4 * ((uint64_t)9 * i + j));
     for (uint32_t j = 0; j < E1_N; ++j) st_zero(e1s + 4 * ((uint64_t)E1_N * i + j));
     for (int j = 0; j < 9; ++j) st_zero(contrib + 4 * ((uint64_t)j * P.count + i));
-    return;
   }
-  const U256 alpha = ldm(ch), beta = ldm(ch + 4), gamma = ldm(ch + 8), v = ldm(ch + 16);
-  const U256 u = ldm(u_in + 4 * (uint64_t)i), rho = ldm(rho_in + 4 * (uint64_t)i);
-  const U256 a_z = ldm(f), b_z = ldm(f + 4), c_z = ldm(f + 8), s1_z = ldm(f + 12), s2_z = ldm(f + 16),
-             r_z = ldm(f + 20), zw_z = ldm(f + 24);
-  // Step 5: L_1(z) = (z^n - 1) / (n (z - 1)); z = 1 has Z_H = 0 and never gets here, so one
-  // inversion of Z_H(z) (z - 1) serves both quotients
-  const U256 zm1 = Fr::sub(zc, one);
-  const U256 zhm = fmul(z_h_z, zm1);
-  U256 tinv, rpi_z = r_z;  // r_z + PI(z)
-  if (PI) {
-    // D_i = prod_j (z w^-j - 1) is nonzero here: a zero factor is z in H, flagged above
-    const U256 piN = u256_from_u64(pi_nd + 8 * (uint64_t)i), piD = u256_from_u64(pi_nd + 8 * (uint64_t)i + 4);
-    const U256 all = vb_inv(fmul(zhm, piD), one);
-    tinv = fmul(all, piD);
-    rpi_z = Fr::sub(r_z, fmul(fmul(fmul(z_h_z, P.n_inv), piN), fmul(all, zhm)));
-  } else {
-    tinv = vb_inv(zhm, one);
-  }
-  const U256 inv_zh = fmul(tinv, zm1);
-  const U256 l1 = fmul(fmul(z_h_z, fmul(tinv, z_h_z)), P.n_inv);
-  // Step 7: t_z
-  const U256 alpha2 = fmul(alpha, alpha);
-  const U256 l1a2 = fmul(l1, alpha2);
-  const U256 pa = Fr::add(Fr::add(a_z, fmul(beta, s1_z)), gamma);
-  const U256 pb = Fr::add(Fr::add(b_z, fmul(beta, s2_z)), gamma);
-  const U256 pab = fmul(pa, pb);
-  U256 perm = fmul(pab, fmul(Fr::add(c_z, gamma), zw_z));
-  if (P.mode == 1) perm = fmul(perm, alpha);
-  const U256 t_z = fmul(Fr::sub(Fr::sub(rpi_z, perm), l1a2), inv_zh);
-  // Steps 8-10
-  U256 vp[7];
-  vp[0] = one;
-  for (int k = 1; k < 7; ++k) vp[k] = fmul(vp[k - 1], v);
-  const U256 bz = fmul(beta, zc);
-  const U256 d2 = Fr::add(
-      Fr::add(fmul(fmul(fmul(fmul(Fr::add(Fr::add(a_z, bz), gamma), Fr::add(Fr::add(b_z, fmul(bz, P.k1)), gamma)),
-                             Fr::add(Fr::add(c_z, fmul(bz, P.k2)), gamma)),
-                        alpha),
-                   v),
-              fmul(l1a2, v)),
-      u);
-  const U256 d3 = fmul(fmul(fmul(fmul(pab, alpha), v), beta), zw_z);
-  U256 ecoef = Fr::add(t_z, fmul(v, r_z));
-  ecoef = Fr::add(ecoef, fmul(vp[2], a_z));
-  ecoef = Fr::add(ecoef, fmul(vp[3], b_z));
-  ecoef = Fr::add(ecoef, fmul(vp[4], c_z));
-  ecoef = Fr::add(ecoef, fmul(vp[5], s1_z));
-  ecoef = Fr::add(ecoef, fmul(vp[6], s2_z));
-  ecoef = Fr::add(ecoef, fmul(u, zw_z));
-  const U256 zn2 = fmul(zn, fmul(zc, zc));  // z^(n+2)
-  const U256 zero = u256_zero();
-  uint64_t* o = sc + 4 * (uint64_t)9 * i;
-  stm(o, fmul(rho, vp[2]));                       // a_s
-  stm(o + 4, fmul(rho, vp[3]));                   // b_s
-  stm(o + 8, fmul(rho, vp[4]));                   // c_s
-  stm(o + 12, fmul(rho, d2));                     // z_s
-  stm(o + 16, rho);                               // t_lo
-  stm(o + 20, fmul(rho, zn2));                    // t_mid
-  stm(o + 24, fmul(rho, fmul(zn2, zn2)));         // t_hi: z^(2n+4)
-  stm(o + 28, fmul(rho, zc));                     // w_z * z
-  const U256 ru = fmul(rho, u);
-  stm(o + 32, fmul(ru, fmul(zc, P.omega)));       // w_zw * u z w
-  for (uint32_t j = 0; j < E1_AT; ++j) st_zero(e1s + 4 * ((uint64_t)E1_N * i + j));
-  stm(e1s + 4 * ((uint64_t)E1_N * i + E1_AT), rho);
-  stm(e1s + 4 * ((uint64_t)E1_N * i + E1_AT + 1), ru);
-  const U256 rv = fmul(rho, v);
-  const uint64_t cs = (uint64_t)4 * P.count;
-  uint64_t* c = contrib + 4 * (uint64_t)i;
-  stm(c, fmul(rv, fmul(a_z, b_z)));               // q_m
-  stm(c + cs, fmul(rv, a_z));                     // q_l
-  stm(c + 2 * cs, fmul(rv, b_z));                 // q_r
-  stm(c + 3 * cs, fmul(rv, c_z));                 // q_o
-  stm(c + 4 * cs, rv);                            // q_c
-  stm(c + 5 * cs, fmul(rho, vp[5]));              // s1
-  stm(c + 6 * cs, fmul(rho, vp[6]));              // s2
-  stm(c + 7 * cs, Fr::sub(zero, fmul(rho, d3)));  // - s3 d3
-  stm(c + 8 * cs, Fr::sub(zero, fmul(rho, ecoef)));  // - E
 }
 
 // ---- public inputs: PI(z) = -(z^n - 1)/n * S, S = sum_{j<npub} pub_j w^j / (z - w^j) = sum_j pub_j / (z w^-j - 1)
@@ -343,13 +260,7 @@ struct Batch {
     uint64_t e1[8], e2[8];
     if ((rc = pbf_msm_g1_bn254_dev(ctx, P, S, 9 * len + 9, e2, s))) return rc;
     if ((rc = pbf_msm_g1_bn254_dev(ctx, e1p + 16 * lo, e1s + 4 * E1_N * lo, E1_N * len, e1, s))) return rc;
-    // e(sum rho E1, [s]G2) e(-sum rho E2, G2) == 1
-    uint64_t g1s[16], g2s[32];
-    memcpy(g1s, e1, 64);
-    neg_g1(e2, g1s + 8);
-    memcpy(g2s, g2 + 16, 128);  // [s]G2
-    memcpy(g2s + 16, g2, 128);  // G2
-    return pairing_check_on_stream(ctx, g1s, g2s, 2, ok, s);
+    return pairing_tail(ctx, e1, e2, g2, ok, s);  // e(sum rho E1, [s]G2) e(-sum rho E2, G2) == 1
   }
 
   // ok_each over [lo, hi) by halving. failed: the range's equation is already known to fail
@@ -379,11 +290,8 @@ struct Batch {
 int vb_validate(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies, const uint64_t* srs, size_t srs_m,
                 const uint64_t* g2, size_t count, const uint64_t* proof_pts, const uint64_t* proof_f,
                 const uint64_t* chal, const uint64_t* u, const uint64_t* rho, const uint64_t* k1k2, int* ok) {
-  if (!ctx || !q || !copies || !srs || !g2 || !proof_pts || !proof_f || !chal || !u || !rho || !k1k2 || !ok)
-    return fail(PBF_EINVAL, "null argument");
-  *ok = 0;
-  if (n < 8 || (n & (n - 1))) return fail(PBF_EINVAL, "n must be a power of two >= 8");
-  if (srs_m < n) return fail(PBF_EINVAL, "SRS too short");
+  int rc = verifier_shape({ctx, q, copies, srs, g2, proof_pts, proof_f, chal, u, rho, k1k2}, n, srs_m, ok);
+  if (rc) return rc;
   if (count == 0 || count > ((size_t)1 << 20)) return fail(PBF_EINVAL, "count must be in 1 .. 2^20");
   for (size_t i = 0; i < count; ++i) {
     const uint64_t* r = rho + 4 * i;
@@ -441,12 +349,10 @@ static int vb_run(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d
       (rc = plonk_pub_validate(n, pub, npub, count)))
     return rc;
   PBF_HIP(hipSetDevice(ctx->device));
-  uint32_t log_n = 0;
-  while ((1ull << log_n) < n) ++log_n;
   hipStream_t s = (hipStream_t)stream;
-  const U256 omega = fr_root_of_unity(log_n);
+  const PlonkDomain dom = plonk_domain(n);
   uint64_t pre[8][8];
-  if ((rc = verifier_vk(ctx, n, omega, d_q, d_copies, d_srs, srs_m, k1k2, s, pre))) return rc;
+  if ((rc = verifier_vk(ctx, n, dom.omega, d_q, d_copies, d_srs, srs_m, k1k2, s, pre))) return rc;
 
   const size_t c = count;
   DevBuf &bp = ctx->buf("vb.pts"), &bs = ctx->buf("vb.sc"), &bf = ctx->buf("vb.f"), &bc = ctx->buf("vb.chal"),
@@ -467,23 +373,7 @@ static int vb_run(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d
   PBF_HIP(hipMemcpyAsync(bu.p, u, c * 32, hipMemcpyHostToDevice, s));
   PBF_HIP(hipMemcpyAsync(br.p, rho, c * 32, hipMemcpyHostToDevice, s));
   PBF_HIP(hipMemsetAsync(bfl.p, 0, c * sizeof(int), s));
-  VbParams P;
-  P.k1 = Fr::to_mont(u256_from_u64(k1k2));
-  P.k2 = Fr::to_mont(u256_from_u64(k1k2 + 4));
-  P.omega = omega;
-  {  // n^-1 = (2^-1)^log_n, 2^-1 = (r + 1) / 2
-    U256 h;
-    for (int i = 0; i < 8; ++i) h.w[i] = Bn254FrParams::P[i];
-    h.w[0] += 1;  // r is odd and its low limb is not all ones: no carry
-    for (int i = 0; i < 8; ++i) h.w[i] = (h.w[i] >> 1) | (i < 7 ? (h.w[i + 1] << 31) : 0);
-    const U256 half = Fr::to_mont(h);
-    U256 ni = Fr::to_mont(Fr::one_plain());
-    for (uint32_t k = 0; k < log_n; ++k) ni = Fr::mul(ni, half);
-    P.n_inv = ni;
-  }
-  P.log_n = log_n;
-  P.count = (uint32_t)c;
-  P.mode = mode;
+  const VbParams P{hm(k1k2), hm(k1k2 + 4), dom, (uint32_t)c, mode};
   const uint32_t npts = (uint32_t)(9 * c);
   hipLaunchKernelGGL(k_vb_curve, dim3((npts + 255) / 256), dim3(256), 0, s, (const uint64_t*)pts, npts, (int*)bfl.p,
                      (uint64_t*)bq.p);
@@ -491,7 +381,7 @@ static int vb_run(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d
     DevBuf &bpub = ctx->buf("vb.pub"), &bnd = ctx->buf("vb.pind");
     if ((rc = bpub.ensure(c * npub * 32)) || (rc = bnd.ensure(c * 64))) return rc;
     PBF_HIP(hipMemcpyAsync(bpub.p, pub, c * npub * 32, hipMemcpyHostToDevice, s));
-    if ((rc = plonk_pi_fraction_run(ctx, omega, (const uint64_t*)bpub.p, npub, (const uint64_t*)bc.p, c,
+    if ((rc = plonk_pi_fraction_run(ctx, dom.omega, (const uint64_t*)bpub.p, npub, (const uint64_t*)bc.p, c,
                                     (uint64_t*)bnd.p, s)))
       return rc;
     hipLaunchKernelGGL(k_vb_scalars<true>, dim3((uint32_t)((c + 63) / 64)), dim3(64), 0, s, (const uint64_t*)bf.p,
@@ -561,11 +451,8 @@ extern "C" int pbf_plonk_verify_bn254_batch_pi(pbf_ctx* ctx, size_t n, const uin
     return rc;
   PBF_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->host_stream();
-  DevBuf &dq = ctx->buf("vf.q"), &dc = ctx->buf("vf.copies"), &dsrs = ctx->buf("vf.srs");
-  if ((rc = dq.ensure(5 * n * 32)) || (rc = dc.ensure(3 * n * 16)) || (rc = dsrs.ensure(srs_m * 64))) return rc;
-  PBF_HIP(hipMemcpyAsync(dq.p, q, 5 * n * 32, hipMemcpyHostToDevice, s));
-  PBF_HIP(hipMemcpyAsync(dc.p, copies, 3 * n * 16, hipMemcpyHostToDevice, s));
-  PBF_HIP(hipMemcpyAsync(dsrs.p, srs, srs_m * 64, hipMemcpyHostToDevice, s));
-  return vb_run(ctx, n, (const uint64_t*)dq.p, (const uint64_t*)dc.p, (const uint64_t*)dsrs.p, srs_m, g2, count,
-                proof_pts, proof_f, pub, npub, chal, u, rho, k1k2, mode, ok, ok_each, s);
+  const uint64_t *d_q, *d_copies, *d_srs;
+  if ((rc = verifier_upload(ctx, n, q, copies, srs, srs_m, s, &d_q, &d_copies, &d_srs))) return rc;
+  return vb_run(ctx, n, d_q, d_copies, d_srs, srs_m, g2, count, proof_pts, proof_f, pub, npub, chal, u, rho, k1k2, mode, ok,
+                ok_each, s);
 }

@@ -449,10 +449,7 @@ class Context:
         idx); abc: 3 columns; chal: (alpha, beta, gamma, z, v); rnd: b1..b9; srs: affine points.
         Returns (9 points, 7 field ints) as Proof (plonk.rs:61-95)."""
         n = len(abc[0])
-        qa = ints_to_limbs([x for col in q for x in col])
-        ca = np.array([v for col in copies for (k, i) in col for v in (k, i)], dtype=np.uint64)
-        aa = ints_to_limbs([x for col in abc for x in col])
-        sa = _g1_limbs(srs)
+        qa, ca, aa, sa = _circuit_limbs(q, copies, srs, abc)
         pts = np.zeros(72, dtype=np.uint64)
         fs = np.zeros(28, dtype=np.uint64)
         _check(self.lib.pbf_plonk_prove_bn254(self.h, n, _ptr(qa), _ptr(ca), _ptr(aa), _ptr(ints_to_limbs(chal)),
@@ -463,16 +460,7 @@ class Context:
             limbs_to_ints(fs)
 
     def plonk_verify_bn254(self, q, copies, srs, g2s, pts, fields, chal, u, k1k2=(2, 3), mode=0) -> bool:
-        n = len(q[0])
-        qa = ints_to_limbs([x for col in q for x in col])
-        ca = np.array([v for col in copies for (k, i) in col for v in (k, i)], dtype=np.uint64)
-        sa = _g1_limbs(srs)
-        ok = ctypes.c_int(-1)
-        _check(self.lib.pbf_plonk_verify_bn254(self.h, n, _ptr(qa), _ptr(ca), _ptr(sa), len(srs), _ptr(_g2_limbs(g2s)),
-                                               _ptr(_g1_limbs(pts)), _ptr(ints_to_limbs(fields)),
-                                               _ptr(ints_to_limbs(chal)), _ptr(ints_to_limbs([u])),
-                                               _ptr(ints_to_limbs(k1k2)), mode, ctypes.byref(ok)))
-        return ok.value == 1
+        return self.plonk_verify_bn254_pi(q, copies, srs, g2s, pts, fields, None, chal, u, k1k2, mode)
 
     def plonk_synth_circuit_dev(self, n, seed, d_q, d_copies, d_abc, stream: int = 0) -> None:
         _check(self.lib.pbf_plonk_synth_circuit_bn254_dev(self.h, n, seed, d_q, d_copies, d_abc, stream))
@@ -493,15 +481,8 @@ class Context:
                                mode=0, stream: int = 0) -> bool:
         """Plonk::verify (plonk.rs:468-650) with the circuit and SRS on the device; pts / fields
         as plonk_prove_bn254_dev returns them (limb arrays) or as ints / points."""
-        pa = pts if isinstance(pts, np.ndarray) else _g1_limbs(pts)
-        fa = fields if isinstance(fields, np.ndarray) else ints_to_limbs(fields)
-        ok = ctypes.c_int(-1)
-        _check(self.lib.pbf_plonk_verify_bn254_dev(self.h, n, d_q, d_copies, d_srs, srs_m, _ptr(_g2_limbs(g2s)),
-                                                   _ptr(np.ascontiguousarray(pa, dtype=np.uint64)),
-                                                   _ptr(np.ascontiguousarray(fa, dtype=np.uint64)),
-                                                   _ptr(ints_to_limbs(chal)), _ptr(ints_to_limbs([u])),
-                                                   _ptr(ints_to_limbs(k1k2)), mode, ctypes.byref(ok), stream))
-        return ok.value == 1
+        return self.plonk_verify_bn254_pi_dev(n, d_q, d_copies, d_srs, srs_m, g2s, pts, fields, None, chal, u, k1k2,
+                                              mode, stream)
 
     @staticmethod
     def _batch_arrays(proofs, chals, us, rhos):
@@ -513,8 +494,7 @@ class Context:
         pa = np.zeros(72 * count, dtype=np.uint64)
         fa = np.zeros(28 * count, dtype=np.uint64)
         for i, (pts, fields) in enumerate(proofs):
-            pa[72 * i:72 * i + 72] = pts if isinstance(pts, np.ndarray) else _g1_limbs(pts)
-            fa[28 * i:28 * i + 28] = fields if isinstance(fields, np.ndarray) else ints_to_limbs(fields)
+            pa[72 * i:72 * i + 72], fa[28 * i:28 * i + 28] = _proof_limbs(pts, fields)
         ca = ints_to_limbs([x for ch in chals for x in ch]) if count else np.zeros(0, dtype=np.uint64)
         ua = ints_to_limbs(list(us)) if count else np.zeros(0, dtype=np.uint64)
         ra = ints_to_limbs(list(rhos)) if count else np.zeros(0, dtype=np.uint64)
@@ -525,30 +505,14 @@ class Context:
         """pbf_plonk_verify_bn254_batch: many proofs of one circuit, one pairing check. rhos are the
         batching weights: nonzero, < r, chosen unpredictably after seeing the proofs (soundness
         rests on that; include/pbf.h). Returns ok, or (ok, [ok_i]) with each=True."""
-        n = len(q[0])
-        qa = ints_to_limbs([x for col in q for x in col])
-        ca = np.array([v for col in copies for (k, i) in col for v in (k, i)], dtype=np.uint64)
-        sa = _g1_limbs(srs)
-        count, pa, fa, cha, ua, ra = self._batch_arrays(proofs, chals, us, rhos)
-        ok = ctypes.c_int(-1)
-        oe = (ctypes.c_int * max(count, 1))() if each else None
-        _check(self.lib.pbf_plonk_verify_bn254_batch(self.h, n, _ptr(qa), _ptr(ca), _ptr(sa), len(srs),
-                                                     _ptr(_g2_limbs(g2s)), count, _ptr(pa), _ptr(fa), _ptr(cha),
-                                                     _ptr(ua), _ptr(ra), _ptr(ints_to_limbs(k1k2)), mode,
-                                                     ctypes.byref(ok), oe))
-        return (ok.value == 1, [bool(v) for v in oe[:count]]) if each else ok.value == 1
+        return self.plonk_verify_bn254_batch_pi(q, copies, srs, g2s, proofs, [()] * len(proofs), chals, us, rhos, k1k2,
+                                                mode, each)
 
     def plonk_verify_bn254_batch_dev(self, n, d_q, d_copies, d_srs, srs_m, g2s, proofs, chals, us, rhos,
                                      k1k2=(2, 3), mode=0, each=False, stream: int = 0):
         """The same with the circuit and SRS on the device (shaped like plonk_verify_bn254_dev)."""
-        count, pa, fa, cha, ua, ra = self._batch_arrays(proofs, chals, us, rhos)
-        ok = ctypes.c_int(-1)
-        oe = (ctypes.c_int * max(count, 1))() if each else None
-        _check(self.lib.pbf_plonk_verify_bn254_batch_dev(self.h, n, d_q, d_copies, d_srs, srs_m,
-                                                         _ptr(_g2_limbs(g2s)), count, _ptr(pa), _ptr(fa), _ptr(cha),
-                                                         _ptr(ua), _ptr(ra), _ptr(ints_to_limbs(k1k2)), mode,
-                                                         ctypes.byref(ok), oe, stream))
-        return (ok.value == 1, [bool(v) for v in oe[:count]]) if each else ok.value == 1
+        return self.plonk_verify_bn254_batch_pi_dev(n, d_q, d_copies, d_srs, srs_m, g2s, proofs, [()] * len(proofs),
+                                                    chals, us, rhos, k1k2, mode, each, stream)
 
     # ---- public inputs (include/pbf.h "Public inputs"): pub_i on gate row i < npub, one circuit for
     # many statements. pub: ints (or None with npub = 0); npub defaults to len(pub).
@@ -572,10 +536,7 @@ class Context:
     def plonk_prove_bn254_pi(self, q, copies, abc, pub, chal, rnd, srs, k1k2=(2, 3), mode=0, npub=None):
         """plonk_prove_bn254 with public inputs: row i < npub satisfies ... + q_c - pub_i = 0."""
         n = len(abc[0])
-        qa = ints_to_limbs([x for col in q for x in col])
-        ca = np.array([v for col in copies for (k, i) in col for v in (k, i)], dtype=np.uint64)
-        aa = ints_to_limbs([x for col in abc for x in col])
-        sa = _g1_limbs(srs)
+        qa, ca, aa, sa = _circuit_limbs(q, copies, srs, abc)
         _keep, pp, npub = self._pub_arg(pub, npub)
         pts = np.zeros(72, dtype=np.uint64)
         fs = np.zeros(28, dtype=np.uint64)
@@ -601,14 +562,13 @@ class Context:
     def plonk_verify_bn254_pi(self, q, copies, srs, g2s, pts, fields, pub, chal, u, k1k2=(2, 3), mode=0,
                               npub=None) -> bool:
         n = len(q[0])
-        qa = ints_to_limbs([x for col in q for x in col])
-        ca = np.array([v for col in copies for (k, i) in col for v in (k, i)], dtype=np.uint64)
-        sa = _g1_limbs(srs)
+        qa, ca, sa = _circuit_limbs(q, copies, srs)
+        pa, fa = _proof_limbs(pts, fields)
         _keep, pp, npub = self._pub_arg(pub, npub)
         ok = ctypes.c_int(-1)
         _check(self.lib.pbf_plonk_verify_bn254_pi(self.h, n, _ptr(qa), _ptr(ca), _ptr(sa), len(srs),
-                                                  _ptr(_g2_limbs(g2s)), _ptr(_g1_limbs(pts)),
-                                                  _ptr(ints_to_limbs(fields)), pp, npub, _ptr(ints_to_limbs(chal)),
+                                                  _ptr(_g2_limbs(g2s)), _ptr(pa), _ptr(fa), pp, npub,
+                                                  _ptr(ints_to_limbs(chal)),
                                                   _ptr(ints_to_limbs([u])), _ptr(ints_to_limbs(k1k2)), mode,
                                                   ctypes.byref(ok)))
         return ok.value == 1
@@ -616,13 +576,11 @@ class Context:
     def plonk_verify_bn254_pi_dev(self, n, d_q, d_copies, d_srs, srs_m, g2s, pts, fields, pub, chal, u, k1k2=(2, 3),
                                   mode=0, stream: int = 0, npub=None) -> bool:
         """The circuit and SRS on the device; the proof and pub on the host."""
-        pa = pts if isinstance(pts, np.ndarray) else _g1_limbs(pts)
-        fa = fields if isinstance(fields, np.ndarray) else ints_to_limbs(fields)
+        pa, fa = _proof_limbs(pts, fields)
         _keep, pp, npub = self._pub_arg(pub, npub)
         ok = ctypes.c_int(-1)
         _check(self.lib.pbf_plonk_verify_bn254_pi_dev(self.h, n, d_q, d_copies, d_srs, srs_m, _ptr(_g2_limbs(g2s)),
-                                                      _ptr(np.ascontiguousarray(pa, dtype=np.uint64)),
-                                                      _ptr(np.ascontiguousarray(fa, dtype=np.uint64)), pp, npub,
+                                                      _ptr(pa), _ptr(fa), pp, npub,
                                                       _ptr(ints_to_limbs(chal)), _ptr(ints_to_limbs([u])),
                                                       _ptr(ints_to_limbs(k1k2)), mode, ctypes.byref(ok), stream))
         return ok.value == 1
@@ -632,9 +590,7 @@ class Context:
         """plonk_verify_bn254_batch over proofs of one circuit with a statement each: pubs[i] the
         public inputs of proofs[i]."""
         n = len(q[0])
-        qa = ints_to_limbs([x for col in q for x in col])
-        ca = np.array([v for col in copies for (k, i) in col for v in (k, i)], dtype=np.uint64)
-        sa = _g1_limbs(srs)
+        qa, ca, sa = _circuit_limbs(q, copies, srs)
         count, pa, fa, cha, ua, ra = self._batch_arrays(proofs, chals, us, rhos)
         if len(pubs) != count:
             raise ValueError("one list of public inputs per proof")
@@ -1170,6 +1126,22 @@ BN254_R = 2188824287183927522224640574525727508854836440041603434369820418657580
 BN254_Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583
 
 
+def _circuit_limbs(q, copies, srs, abc=None):
+    """The limb arrays of a host circuit and SRS, (qa, ca, sa) or with a witness (qa, ca, aa, sa): q 5
+    columns of ints, copies 3 columns of (kind, 1-based idx), abc 3 columns, srs affine points."""
+    qa = ints_to_limbs([x for col in q for x in col])
+    ca = np.array([v for col in copies for (k, i) in col for v in (k, i)], dtype=np.uint64)
+    sa = _g1_limbs(srs)
+    return (qa, ca, sa) if abc is None else (qa, ca, ints_to_limbs([x for col in abc for x in col]), sa)
+
+
+def _proof_limbs(pts, fields):
+    """(72, 28) u64 limbs of a proof given as the provers return it: limb arrays, or points and ints."""
+    pa = pts if isinstance(pts, np.ndarray) else _g1_limbs(pts)
+    fa = fields if isinstance(fields, np.ndarray) else ints_to_limbs(fields)
+    return np.ascontiguousarray(pa, dtype=np.uint64), np.ascontiguousarray(fa, dtype=np.uint64)
+
+
 def _g1_limbs(pts) -> np.ndarray:
     return ints_to_limbs([c for p in pts for c in ((0, 0) if p is None else p)])
 
@@ -1267,10 +1239,7 @@ def plonk_prove_bn254_multi(ctxs, q, copies, abc, chal, rnd, srs, k1k2=(2, 3), m
     """pbf_plonk_prove_bn254_multi (host inputs; same conventions as Context.plonk_prove_bn254)."""
     arr, w = _ctx_array(ctxs)
     n = len(abc[0])
-    qa = ints_to_limbs([x for col in q for x in col])
-    ca = np.array([v for col in copies for (k, i) in col for v in (k, i)], dtype=np.uint64)
-    aa = ints_to_limbs([x for col in abc for x in col])
-    sa = _g1_limbs(srs)
+    qa, ca, aa, sa = _circuit_limbs(q, copies, srs, abc)
     pts = np.zeros(72, dtype=np.uint64)
     fs = np.zeros(28, dtype=np.uint64)
     _check(load_library().pbf_plonk_prove_bn254_multi(arr, w, n, _ptr(qa), _ptr(ca), _ptr(aa), _ptr(ints_to_limbs(chal)),

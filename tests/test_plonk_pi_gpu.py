@@ -337,3 +337,47 @@ def test_argument_errors_leave_the_context_usable(ctx, gold_srs):
     einval(lambda: batch(not_canonical))
     einval(lambda: ctx.plonk_verify_bn254_batch_pi(c["q"], c["copies"], srs, g2s, [want], [too_many], [c["chal"]], [5],
                                                    [7], mode=1))
+
+
+# ---------------------------------------------------------------- the single verifier and a batch of one
+# Both run plonk_verifier_scalars (csrc/plonk_terms.hpp), one on the host with rho = 1, one in
+# k_vb_scalars: the same verdict, and the oracle's (tests/golden/plonk_verify_shapes.json, recorded
+# from plonk_pi_expect.verify by tests/golden/gen_plonk_verify_shapes.py), at n = 8 and at n = 128,
+# in both modes, without and with public inputs.
+SHAPES = json.load(open(os.path.join(ROOT, "tests", "golden", "plonk_verify_shapes.json")))["cases"]
+
+
+@pytest.fixture(scope="module")
+def shape_srs(ctx):
+    return {n: (ctx.srs_create(E.S_SECRET, n + 3), _g2s(ctx, E.S_SECRET)) for n in (8, 128)}
+
+
+def test_shapes_cover_the_cases():
+    assert [(c["n"], c["mode"], c["npub"]) for c in SHAPES] == \
+        [(n, m, k) for n in (8, 128) for m in ("reference", "paper") for k in (0, 3)]
+    assert all(c["s"] == E.S_SECRET and len(c["pub"]) == c["npub"] for c in SHAPES)
+
+
+@pytest.mark.parametrize("case", SHAPES, ids=[f"n{c['n']}-npub{c['npub']}-{c['mode']}" for c in SHAPES])
+def test_single_verifier_and_batch_of_one_give_the_oracles_verdict(ctx, shape_srs, case):
+    n, mode, pub, chal, u = case["n"], MODES[case["mode"]], case["pub"], case["chal"], case["u"]
+    q, cp, _a, _b = E.scale_circuit(n, case["seed"])
+    srs, g2s = shape_srs[n]
+    pts, fs = [_pt(p) for p in case["pts"]], case["fields"]
+    rho = random.Random(case["seed"]).randrange(1, R)
+
+    def verdict(pts=pts, fs=fs, chal=chal):
+        """PBF_OK from both (an error would raise), and one verdict."""
+        one = ctx.plonk_verify_bn254_pi(q, cp, srs, g2s, pts, fs, pub, chal, u, mode=mode)
+        assert ctx.plonk_verify_bn254_batch_pi(q, cp, srs, g2s, [(pts, fs)], [pub], [chal], [u], [rho], mode=mode,
+                                               each=True) == (one, [one])
+        return one
+
+    want = case["verdicts"]
+    assert want["valid"] is (mode == 1)  # an honest reference-mode proof does not verify (SURVEY 0.7)
+    assert verdict() is want["valid"]
+    assert verdict(fs=[(fs[0] + 1) % R] + fs[1:]) is want["a_z"] is False
+    off = list(pts)
+    off[7] = (off[7][0], (off[7][1] + 1) % B.Q)
+    assert verdict(pts=off) is want["off_curve"] is False
+    assert verdict(chal=chal[:3] + [F.root_of_unity(n)] + chal[4:]) is want["z_omega"] is False
