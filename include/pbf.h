@@ -326,10 +326,11 @@ int pbf_plonk_verify_bn254_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, cons
  * (alpha beta gamma z v per proof), u count x 4, rho count x 4. The circuit, SRS, g2, k1k2,
  * mode, the stream contract, the verification-key cache and option verifier.vk are those of
  * pbf_plonk_verify_bn254 / _dev.
- * Randomness: the library reads none. Soundness rests on the caller choosing the weights rho
- * unpredictably and AFTER seeing the proofs (e.g. by hashing all of them); with predictable or
- * equal weights the errors of two bad proofs can cancel and the batch passes. rho_0 = 1 is
- * fine; 128-bit weights are enough.
+ * Randomness: the library reads none. In this form soundness rests on the caller choosing the
+ * weights rho unpredictably and AFTER seeing the proofs; with predictable or equal weights the
+ * errors of two bad proofs can cancel and the batch passes. rho_0 = 1 is fine; 128-bit weights are
+ * enough. pbf_plonk_verify_bn254_batch_fs ("Fiat-Shamir" below) takes no rho: it derives the
+ * weights, with chal and u, by hashing all the proofs on the device.
  * Result: a proof is rejected outright when one of its 9 points is not canonical or not on the
  * curve ((0,0) is accepted), one of its 7 fields is >= r, or Z_H(z_i) = 0 -- the single
  * verifier's ok = 0 cases. *ok = 1 iff no proof is rejected and the combined check passes.
@@ -381,8 +382,8 @@ int pbf_plonk_verify_bn254_batch_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q
  *     nothing. The prover forms q_c(x) + PI(x) on the coset in per-proof scratch it already owns
  *     (one INTT of n and one coset NTT of 4n per proof; no added buffer); the key's q_c slot is
  *     never written, and a _pi call does not alter what a later plain call returns on the context.
- *   - Soundness: the library derives no challenge (as with rho below), so the caller's transcript
- *     must absorb pub before beta.
+ *   - Soundness: these entries derive no challenge, so the caller's transcript must absorb pub
+ *     before beta; the _fs forms ("Fiat-Shamir" below) do, and theirs does.
  *   - the sharded and _multi provers take no public inputs.                                      */
 int pbf_plonk_prove_bn254_pi(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies, const uint64_t* abc,
                              const uint64_t* pub, size_t npub, const uint64_t* chal, const uint64_t* rnd,
@@ -412,6 +413,111 @@ int pbf_plonk_verify_bn254_batch_pi_dev(pbf_ctx* ctx, size_t n, const uint64_t* 
                                         const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* pub,
                                         size_t npub, const uint64_t* chal, const uint64_t* u, const uint64_t* rho,
                                         const uint64_t* k1k2, int mode, int* ok, int* ok_each, void* stream);
+
+/* ---- Fiat-Shamir: a Keccak-256 transcript, derived challenges ------------------------------
+ * The entry points above take alpha beta gamma z v, u and rho from the caller. For the prover no
+ * caller can choose them soundly: beta and gamma must depend on a_s b_s c_s, alpha on z_s, z on the
+ * t commitments, all outputs of the same call. The _fs forms below take no challenge: they derive
+ * them from the transcript fixed here (normative), so prove_fs returns a
+ * non-interactive proof and verify_fs / verify_batch_fs check one.
+ *
+ * H is Keccak-256 (rate 136 bytes, padding 0x01 .. 0x80, 32-byte digest: Ethereum's variant, not
+ * SHA3-256). All integers are big-endian: u64(k) is 8 bytes; be32(x) is 32 bytes, for an Fr value
+ * or an Fq coordinate, from the canonical 4 x u64 limbs; pt(P) = be32(x) | be32(y), the identity
+ * (0,0) being 64 zero bytes. A challenge is int(digest) mod r. Every item is a multiple of 8
+ * bytes, so a message is a sequence of whole Keccak lanes.
+ *   Tree digest of m 32-byte items under tag g: root = 32 zero bytes if m = 0; otherwise replace the
+ *   items by H(c_0 | .. | c_k-1) over consecutive groups of 4 (the last group has k = 1..4), repeat,
+ *   at least once, until one item remains: root. The digest is H(u64(g) | u64(m) | root); the
+ *   length fixes the tree's shape, so nodes carry no tag.
+ *   Circuit digest (the verification key only):
+ *     h0 = H(D | u64(mode) | u64(n) | u64(npub) | be32(k1) | be32(k2) | pt(q_m) | pt(q_l) | pt(q_r)
+ *            | pt(q_o) | pt(q_c) | pt(s_sigma_1) | pt(s_sigma_2) | pt(s_sigma_3) | G2S)
+ *     D = the 30 ASCII bytes "pbf-plonk-bn254-fiat-shamir-v1" and two zero bytes; the 8 points are
+ *     the verifier's preprocessed commitments; G2S = g2[1] = [s]G2, four coordinates as be32 in the
+ *     order of the 16 x u64 array.
+ *   Per proof (pub, out_pts and out_f orders):
+ *     P  = tree digest, tag 7, of be32(pub_0) .. be32(pub_npub-1)
+ *     t1 = H(h0 | u64(1) | P | pt(a_s) | pt(b_s) | pt(c_s))        beta  = t1 mod r
+ *     t2 = H(t1 | u64(2))                                          gamma = t2 mod r
+ *     t3 = H(t2 | u64(3) | pt(z_s))                                alpha = t3 mod r
+ *     t4 = H(t3 | u64(4) | pt(t_lo) | pt(t_mid) | pt(t_hi))        z     = t4 mod r
+ *     t5 = H(t4 | u64(5) | be32 of the 7 proof fields, in order)   v     = t5 mod r
+ *     t6 = H(t5 | u64(6) | pt(W_z) | pt(W_zw))                     u     = t6 mod r
+ *   Per batch of count proofs: T = tree digest, tag 8, of t6_0 .. t6_count-1;
+ *     rho_i = H(T | u64(9) | u64(i)) mod r, 0 replaced by 1.
+ * The reduction mod r of a 256-bit digest is biased (a residue has 5 or 6 preimages), as in the
+ * on-chain verifiers of this curve. Proof bytes are hashed as given, canonical and on the curve or
+ * not: rejecting them stays the verifier's business, and the transcript has no failing case.
+ *
+ * Where it runs: single proofs (prove_fs, verify_fs, the circuit digest) hash on the host; a batch
+ * (pbf_plonk_challenges_bn254, verify_batch_fs) on the GPU, one lane per proof, next to the proofs
+ * the batch uploads anyway -- its chal, u and rho never exist on the host. Public inputs are hashed
+ * where they are: the prover's d_pub by the tree kernel.
+ *
+ *   pbf_keccak256_batch*: count messages of len >= 0 bytes each, `pitch` >= len bytes apart ->
+ *     out count x 32 bytes. _dev: device pointers (d_out 8-byte aligned), enqueued on `stream`.
+ *   pbf_plonk_circuit_digest_bn254*: h0 (32 bytes, host) of the circuit, SRS, g2, k1k2, mode and
+ *     npub, through the verification key and its cache (pbf_plonk_verify_bn254); no kernel of its own.
+ *   pbf_plonk_challenges_bn254: all host pointers; digest h0; proof_pts count x 9 x 8, proof_f
+ *     count x 7 x 4, pub count x npub x 4 -> chal count x 5 x 4 in the order alpha beta gamma z v
+ *     of the entry points above, u count x 4, rho count x 4 (or NULL: not derived). A caller of the
+ *     plain entry points gets its challenges here.
+ *   pbf_plonk_prove_bn254_fs*: the arguments of _pi / _pi_dev with chal replaced by digest (h0 of
+ *     THIS circuit, SRS and npub: the prover does not check it, a proof under another digest simply
+ *     does not verify), and out_chal: NULL, or 6 x 4 receiving alpha beta gamma z v u. Each round's
+ *     commitments are collected when the round ends and the next challenge derived before the next
+ *     round is enqueued: four collections (slots 0-2, 3, 4-6, 7-8) in place of the plain entry's
+ *     one, so three stream synchronisations more; the launches are otherwise the plain entry's. pbf_plonk_prove_bn254_pi with those challenges returns the
+ *     same proof bit for bit.
+ *   pbf_plonk_verify_bn254_fs*: the arguments of _pi* without chal and u. The circuit digest comes
+ *     from the verification key, so a proof made under another digest fails (ok = 0). pub is hashed
+ *     on one host thread, about npub / 3 permutations at 0.3 us each where measured: 0.11 s at
+ *     npub = 2^20 against a verification of 4 ms. A caller with statements that large verifies
+ *     through the batch form with count = 1, which hashes pub on the device.
+ *   pbf_plonk_verify_bn254_batch_fs*: the arguments of _batch_pi* without chal, u and rho; ok_each
+ *     localises with the derived values.
+ * Errors (PBF_EINVAL, before anything is enqueued): a NULL pointer (pub may be NULL with npub = 0,
+ * out_chal, rho and ok_each are optional), npub > n, a pub value >= r (the prover's _dev form finds
+ * it in its first kernel), count = 0 or > 2^20 (pbf_keccak256_batch*: count = 0 or > 2^37 - 64, one
+ * launch of blocks of 64), count x ceil(npub / 4) > 2^37 - 64, pitch < len. The sharded and _multi provers and the
+ * stand-alone KZG entry points have no transcript (their callers can use pbf_keccak256_batch). */
+int pbf_keccak256_batch(pbf_ctx* ctx, const uint8_t* msgs, size_t count, size_t len, size_t pitch, uint8_t* out);
+int pbf_keccak256_batch_dev(pbf_ctx* ctx, const uint8_t* d_msgs, size_t count, size_t len, size_t pitch,
+                            uint8_t* d_out, void* stream);
+int pbf_plonk_circuit_digest_bn254(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies,
+                                   const uint64_t* srs, size_t srs_m, const uint64_t* g2, const uint64_t* k1k2,
+                                   int mode, size_t npub, uint8_t* digest);
+int pbf_plonk_circuit_digest_bn254_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
+                                       const uint64_t* d_srs, size_t srs_m, const uint64_t* g2, const uint64_t* k1k2,
+                                       int mode, size_t npub, uint8_t* digest, void* stream);
+int pbf_plonk_challenges_bn254(pbf_ctx* ctx, const uint8_t* digest, size_t count, const uint64_t* proof_pts,
+                               const uint64_t* proof_f, const uint64_t* pub, size_t npub, uint64_t* chal, uint64_t* u,
+                               uint64_t* rho);
+int pbf_plonk_prove_bn254_fs(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies, const uint64_t* abc,
+                             const uint64_t* pub, size_t npub, const uint8_t* digest, const uint64_t* rnd,
+                             const uint64_t* k1k2, const uint64_t* srs, size_t srs_m, int mode, uint64_t* out_pts,
+                             uint64_t* out_f, uint64_t* out_chal);
+int pbf_plonk_prove_bn254_fs_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
+                                 const uint64_t* d_abc, const uint64_t* d_pub, size_t npub, const uint8_t* digest,
+                                 const uint64_t* rnd, const uint64_t* k1k2, const uint64_t* d_srs, size_t srs_m,
+                                 int mode, uint64_t* out_pts, uint64_t* out_f, uint64_t* out_chal, void* stream);
+int pbf_plonk_verify_bn254_fs(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies, const uint64_t* srs,
+                              size_t srs_m, const uint64_t* g2, const uint64_t* proof_pts, const uint64_t* proof_f,
+                              const uint64_t* pub, size_t npub, const uint64_t* k1k2, int mode, int* ok);
+int pbf_plonk_verify_bn254_fs_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
+                                  const uint64_t* d_srs, size_t srs_m, const uint64_t* g2, const uint64_t* proof_pts,
+                                  const uint64_t* proof_f, const uint64_t* pub, size_t npub, const uint64_t* k1k2,
+                                  int mode, int* ok, void* stream);
+int pbf_plonk_verify_bn254_batch_fs(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies,
+                                    const uint64_t* srs, size_t srs_m, const uint64_t* g2, size_t count,
+                                    const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* pub,
+                                    size_t npub, const uint64_t* k1k2, int mode, int* ok, int* ok_each);
+int pbf_plonk_verify_bn254_batch_fs_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
+                                        const uint64_t* d_srs, size_t srs_m, const uint64_t* g2, size_t count,
+                                        const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* pub,
+                                        size_t npub, const uint64_t* k1k2, int mode, int* ok, int* ok_each,
+                                        void* stream);
 
 /* ---- KZG commitments over BN254 (the scheme inside Plonk::prove / verify, on its own) ------
  * Elements as above: Fr canonical 4 x u64, G1 affine 8 x u64 with (0,0) the identity, G2 16 x u64;

@@ -35,6 +35,7 @@
 #include <vector>
 #include "../../include/pbf.h"
 #include "prover.hpp"
+#include "transcript.hpp"
 #include "plonk_terms.hpp"
 #include "fr29.hpp"
 
@@ -1140,7 +1141,8 @@ struct Prover {
   }
   // SRS::eval_at_s (plonk.rs:51-58) as a fixed-base MSM against the SRS window table
   // (msm.hpp), its XYZZ result left in device slot `slot` (finish_commits collects all of
-  // them with one copy: the challenges are inputs, nothing waits on a commitment). Sharded:
+  // them with one copy: the challenges are inputs, nothing waits on a commitment; the _fs
+  // entries, whose challenges are derived, collect round by round). Sharded:
   // commit_cr (below), this rank's point range.
   const Affine* srs_tbl = nullptr;
   uint64_t srs_n = 0;
@@ -1301,6 +1303,17 @@ struct Prover {
     PBF_HIP(hipGetLastError());
     return 0;
   }
+  // commitments lo .. hi - 1 as canonical affine points, on one GPU: a round's share of what
+  // finish_commits collects at the end (the _fs entries: the next challenge waits on them)
+  int collect(int lo, int hi, uint64_t (*out)[8]) {
+    Xyzz h[9];
+    int rc = msm_fixed_wait(ctx, s);
+    if (rc) return rc;
+    PBF_HIP(hipMemcpyAsync(h, slots + lo, (size_t)(hi - lo) * sizeof(Xyzz), hipMemcpyDeviceToHost, s));
+    PBF_HIP(hipStreamSynchronize(s));
+    for (int k = lo; k < hi; ++k) xyzz_to_affine_u64(h[k - lo], out[k]);
+    return 0;
+  }
   int finish_commits(int count, uint64_t (*out)[8]) {
     std::vector<Xyzz> h((size_t)count * G);  // [rank][commitment]
     int rc = msm_fixed_wait(ctx, s);
@@ -1341,6 +1354,11 @@ struct ProveState {
   const uint64_t* d_pub = nullptr;  // public inputs (one GPU; npub = 0: none)
   uint64_t npub = 0;
   PlonkChallenges ch;
+  // Fiat-Shamir (pbf_plonk_prove_bn254_fs*, one GPU): the circuit digest h0 in place of challenges;
+  // ch is then filled round by round. out_chal: null, or alpha beta gamma z v u as derived
+  bool fs = false;
+  uint64_t fs_h0[4];
+  uint64_t* out_chal = nullptr;
   U256 bl[9];  // the blinders b1..b9
   // proving key: on (option prover.pk), found valid in the context, and the key to store once built
   bool pk_on = false, pk_hit = false;
@@ -1724,7 +1742,7 @@ static int prove_setup(ProveState& S, pbf_ctx* ctx, const pbf_comm* comm, size_t
   if (log_n + 2 > 28) return fail(PBF_EINVAL, "4n exceeds the 2-adicity of Fr");
   const uint64_t need_srs = mode == 0 ? 2 * n + 2 : n + 3;  // longest committed polynomial
   if (srs_m < need_srs) return fail(PBF_EINVAL, "SRS too short for this n and mode");
-  for (int i = 0; i < 5; ++i)
+  for (int i = 0; chal && i < 5; ++i)
     if (Fr::geq_p(u256_from_u64(chal + 4 * i))) return fail(PBF_EINVAL, "challenge not canonical");
   for (int i = 0; i < 9; ++i)
     if (Fr::geq_p(u256_from_u64(rnd + 4 * i))) return fail(PBF_EINVAL, "blinder not canonical");
@@ -1770,8 +1788,11 @@ static int prove_setup(ProveState& S, pbf_ctx* ctx, const pbf_comm* comm, size_t
   if (heq1(fr_pow(k1, n)) || heq1(fr_pow(k2, n)) || heq1(fr_pow(Fr::mul(k2, fr_inv(k1)), n)) || Fr::is_zero(k1) ||
       Fr::is_zero(k2))
     return fail(PBF_EINVAL, "k1/k2 do not give disjoint cosets of H");
-  S.ch.alpha = hm(chal); S.ch.beta = hm(chal + 4); S.ch.gamma = hm(chal + 8); S.ch.z = hm(chal + 12);
-  S.ch.v = hm(chal + 16); S.ch.k1 = k1; S.ch.k2 = k2;
+  if (chal) {  // null: the _fs entries, whose rounds derive them
+    S.ch.alpha = hm(chal); S.ch.beta = hm(chal + 4); S.ch.gamma = hm(chal + 8); S.ch.z = hm(chal + 12);
+    S.ch.v = hm(chal + 16);
+  }
+  S.ch.k1 = k1; S.ch.k2 = k2;
   for (int i = 0; i < 9; ++i) S.bl[i] = hm(rnd + 4 * i);
 
   ProverBufs& B = S.B;
@@ -1869,6 +1890,17 @@ static int prove_single(ProveState& S) {
   uint64_t* W0 = work;
   uint64_t* W1 = work + 4 * N;
   uint64_t* W2 = work + 8 * N;
+  // Fiat-Shamir (S.fs): a round's commitments are collected when the round ends and its challenge
+  // derived on the host before the next round is enqueued (transcript.hpp; fs_t the running digest)
+  uint64_t(*const opts)[8] = (uint64_t(*)[8])S.out_pts;
+  uint64_t fs_t[4];
+  const auto fs_take = [&](U256& c, const uint64_t* t, int at) {  // c = t mod r, reported at out_chal[at]
+    uint64_t l[4];
+    fs_challenge(t, l);
+    c = hm(l);
+    if (S.out_chal) memcpy(S.out_chal + 4 * at, l, 32);
+    memcpy(fs_t, t, 32);
+  };
 
   // ---- satisfies (constraints.rs:198-230)
   const uint64_t* d_pub = S.d_pub;
@@ -1918,6 +1950,21 @@ static int prove_single(ProveState& S) {
   for (int k = 0; k < 3; ++k)
     if ((rc = P.commit(C(k), n + 2, k))) return rc;
   P.mark("round 1 commits (3 MSM)");
+  if (S.fs) {
+    uint64_t root[4] = {0, 0, 0, 0}, Pd[4], t[4];
+    if (npub) {  // P: the tree digest of pub, its levels on the device where pub is
+      DevBuf& rb = ctx->buf("fs.roots");
+      if ((rc = rb.ensure(32)) || (rc = fs_tree_run(ctx, d_pub, 1, npub, true, (uint64_t*)rb.p, s))) return rc;
+      PBF_HIP(hipMemcpyAsync(root, rb.p, 32, hipMemcpyDeviceToHost, s));
+    }
+    if ((rc = P.collect(0, 3, opts))) return rc;  // synchronises s
+    fs_tree_close(FS_TAG_PUB, npub, root, Pd);
+    fs_round1(S.fs_h0, Pd, opts[0], t);
+    fs_take(S.ch.beta, t, 1);
+    fs_round<0, 0>(fs_t, 2, nullptr, nullptr, t);
+    fs_take(S.ch.gamma, t, 2);
+    P.mark("fs: a_s b_s c_s collected, beta gamma");
+  }
 
   // ---- round 2: accumulator (plonk.rs:278-313)
   uint64_t* acc = (uint64_t*)B.acc.p;
@@ -1946,6 +1993,13 @@ static int prove_single(ProveState& S) {
   P.mark("round 2 accumulator");
   if ((rc = P.commit(zx, n + 3, 3))) return rc;
   P.mark("round 2 commit (MSM)");
+  if (S.fs) {
+    uint64_t t[4];
+    if ((rc = P.collect(3, 4, opts))) return rc;
+    fs_round<1, 0>(fs_t, 3, opts[3], nullptr, t);
+    fs_take(S.ch.alpha, t, 0);
+    P.mark("fs: z_s collected, alpha");
+  }
 
   // ---- round 3: quotient on the coset g H_4n (plonk.rs:326-382)
   const int cmap[13] = {0, 1, 2, -1, 3, 4, 5, 6, 7, 8, 9, 10, -2};  // coef slot per coset slot
@@ -2012,6 +2066,13 @@ static int prove_single(ProveState& S) {
     if ((rc = P.commit(tq + 8 * m, m, 6))) return rc;    // t_hi
   }
   P.mark("round 3 commits (3 MSM)");
+  if (S.fs) {
+    uint64_t t[4];
+    if ((rc = P.collect(4, 7, opts))) return rc;
+    fs_round<3, 0>(fs_t, 4, opts[4], nullptr, t);
+    fs_take(S.ch.z, t, 3);
+    P.mark("fs: t_lo t_mid t_hi collected, z");
+  }
 
   // ---- round 4: evaluations at z (plonk.rs:393-399), linearisation r(x) (:401-422)
   const U256 zw = Fr::mul(zc, P.omega);
@@ -2063,6 +2124,12 @@ static int prove_single(ProveState& S) {
     if ((rc = eval(1, polys, &rlen, &zc, &e.r_z))) return rc;
   }
   P.mark("round 4 evals + r(x)");
+  if (S.fs) {
+    uint64_t t[4];
+    write_proof_fields(S.out_f, e);
+    fs_round<0, 7>(fs_t, 5, nullptr, S.out_f, t);
+    fs_take(S.ch.v, t, 4);
+  }
 
   // ---- round 5: W_z = numerator / (x - z), W_zw = (z(x) - z_w(z)) / (x - z w) (plonk.rs:430-442)
   // by synthetic division on the coefficients
@@ -2080,7 +2147,15 @@ static int prove_single(ProveState& S) {
   if ((rc = P.synth_div(zx, n + 3, zw, e.zw_z, W3, "W_zw division left a remainder (plonk.rs:442)"))) return rc;
   if ((rc = P.commit(W1, wlen, 7))) return rc;
   if ((rc = P.commit(W3, n + 2, 8))) return rc;
-  if ((rc = P.finish_commits(9, (uint64_t(*)[8])S.out_pts))) return rc;
+  if (S.fs) {
+    uint64_t t[4];
+    U256 u;  // for out_chal only: the prover has no use for it
+    if ((rc = P.collect(7, 9, opts))) return rc;
+    fs_round<2, 0>(fs_t, 6, opts[7], nullptr, t);
+    fs_take(u, t, 5);
+  } else if ((rc = P.finish_commits(9, opts))) {
+    return rc;
+  }
   P.mark("round 5 openings + 2 MSM");
   write_proof_fields(S.out_f, e);
   return 0;
@@ -2091,8 +2166,9 @@ static int prove_single(ProveState& S) {
 static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
                       const uint64_t* d_abc, const uint64_t* chal, const uint64_t* rnd, const uint64_t* k1k2,
                       const uint64_t* d_srs, size_t srs_m, int mode, uint64_t* out_pts, uint64_t* out_f,
-                      void* stream, const uint64_t* d_pub = nullptr, size_t npub = 0) {
-  if (!ctx || !d_q || !d_copies || !d_abc || !chal || !rnd || !k1k2 || !d_srs || !out_pts || !out_f)
+                      void* stream, const uint64_t* d_pub = nullptr, size_t npub = 0, const uint8_t* fs_digest = nullptr,
+                      uint64_t* out_chal = nullptr) {
+  if (!ctx || !d_q || !d_copies || !d_abc || (!chal && !fs_digest) || !rnd || !k1k2 || !d_srs || !out_pts || !out_f)
     return fail(PBF_EINVAL, "null argument");
   if (npub && !d_pub) return fail(PBF_EINVAL, "null pub with npub > 0");
   if (npub > n) return fail(PBF_EINVAL, "more public inputs than gates");
@@ -2101,6 +2177,11 @@ static int prove_impl(pbf_ctx* ctx, const pbf_comm* comm, size_t n, const uint64
   S.d_q = d_q; S.d_copies = d_copies; S.d_abc = d_abc;
   S.d_pub = npub ? d_pub : nullptr; S.npub = npub;
   S.out_pts = out_pts; S.out_f = out_f;
+  if (fs_digest) {
+    S.fs = true;
+    S.out_chal = out_chal;
+    memcpy(S.fs_h0, fs_digest, 32);
+  }
   int rc = prove_setup(S, ctx, comm, n, chal, rnd, k1k2, d_srs, srs_m, stream);
   if (rc) return rc;
   return S.P.G > 1 ? prove_sharded(S) : prove_single(S);
@@ -2145,6 +2226,43 @@ extern "C" int pbf_plonk_prove_bn254(pbf_ctx* ctx, size_t n, const uint64_t* q, 
   return 0;
 }
 
+// The host forms with pub (_pi with npub > 0, _fs with any npub): every argument error, the uploads,
+// then the _dev form that chal (_pi) or digest (_fs) selects
+static int prove_host_pub(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies, const uint64_t* abc,
+                          const uint64_t* pub, size_t npub, const uint64_t* chal, const uint8_t* digest,
+                          const uint64_t* rnd, const uint64_t* k1k2, const uint64_t* srs, size_t srs_m, int mode,
+                          uint64_t* out_pts, uint64_t* out_f, uint64_t* out_chal) {
+  if (!ctx || !q || !copies || !abc || !srs) return fail(PBF_EINVAL, "null argument");
+  if (npub && !pub) return fail(PBF_EINVAL, "null pub with npub > 0");
+  if (npub > n) return fail(PBF_EINVAL, "more public inputs than gates");
+  if (npub && !fr_canonical(pub, npub)) return fail(PBF_EINVAL, "public input not canonical");
+  PBF_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->host_stream();
+  DevBuf &dq = ctx->buf("pv.q"), &dc = ctx->buf("pv.copies"), &dabc = ctx->buf("pv.abc"), &dsrs = ctx->buf("pv.srs"),
+         &dpub = ctx->buf("pv.pub");
+  int rc;
+  if ((rc = dq.ensure(5 * n * 32)) || (rc = dc.ensure(3 * n * 16)) || (rc = dabc.ensure(3 * n * 32)) ||
+      (rc = dsrs.ensure(srs_m * 64)) || (rc = dpub.ensure(npub * 32)))
+    return rc;
+  PBF_HIP(hipMemcpyAsync(dq.p, q, 5 * n * 32, hipMemcpyHostToDevice, s));
+  PBF_HIP(hipMemcpyAsync(dc.p, copies, 3 * n * 16, hipMemcpyHostToDevice, s));
+  PBF_HIP(hipMemcpyAsync(dabc.p, abc, 3 * n * 32, hipMemcpyHostToDevice, s));
+  PBF_HIP(hipMemcpyAsync(dsrs.p, srs, srs_m * 64, hipMemcpyHostToDevice, s));
+  if (npub) PBF_HIP(hipMemcpyAsync(dpub.p, pub, npub * 32, hipMemcpyHostToDevice, s));
+  const uint64_t* d_pub = npub ? (const uint64_t*)dpub.p : nullptr;
+  if (digest)
+    rc = pbf_plonk_prove_bn254_fs_dev(ctx, n, (const uint64_t*)dq.p, (const uint64_t*)dc.p, (const uint64_t*)dabc.p,
+                                      d_pub, npub, digest, rnd, k1k2, (const uint64_t*)dsrs.p, srs_m, mode, out_pts,
+                                      out_f, out_chal, s);
+  else
+    rc = pbf_plonk_prove_bn254_pi_dev(ctx, n, (const uint64_t*)dq.p, (const uint64_t*)dc.p, (const uint64_t*)dabc.p,
+                                      d_pub, npub, chal, rnd, k1k2, (const uint64_t*)dsrs.p, srs_m, mode, out_pts, out_f,
+                                      s);
+  if (rc) return rc;
+  PBF_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
 // Public inputs: pub_i on gate row i < npub (pbf.h). One GPU; npub = 0 is the plain entry.
 extern "C" int pbf_plonk_prove_bn254_pi_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
                                             const uint64_t* d_abc, const uint64_t* d_pub, size_t npub,
@@ -2160,29 +2278,28 @@ extern "C" int pbf_plonk_prove_bn254_pi(pbf_ctx* ctx, size_t n, const uint64_t* 
                                         const uint64_t* rnd, const uint64_t* k1k2, const uint64_t* srs, size_t srs_m,
                                         int mode, uint64_t* out_pts, uint64_t* out_f) {
   if (!npub) return pbf_plonk_prove_bn254(ctx, n, q, copies, abc, chal, rnd, k1k2, srs, srs_m, mode, out_pts, out_f);
-  if (!ctx || !q || !copies || !abc || !srs) return fail(PBF_EINVAL, "null argument");
-  if (!pub) return fail(PBF_EINVAL, "null pub with npub > 0");
-  if (npub > n) return fail(PBF_EINVAL, "more public inputs than gates");
-  if (!fr_canonical(pub, npub)) return fail(PBF_EINVAL, "public input not canonical");
-  PBF_HIP(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->host_stream();
-  DevBuf &dq = ctx->buf("pv.q"), &dc = ctx->buf("pv.copies"), &dabc = ctx->buf("pv.abc"), &dsrs = ctx->buf("pv.srs"),
-         &dpub = ctx->buf("pv.pub");
-  int rc;
-  if ((rc = dq.ensure(5 * n * 32)) || (rc = dc.ensure(3 * n * 16)) || (rc = dabc.ensure(3 * n * 32)) ||
-      (rc = dsrs.ensure(srs_m * 64)) || (rc = dpub.ensure(npub * 32)))
-    return rc;
-  PBF_HIP(hipMemcpyAsync(dq.p, q, 5 * n * 32, hipMemcpyHostToDevice, s));
-  PBF_HIP(hipMemcpyAsync(dc.p, copies, 3 * n * 16, hipMemcpyHostToDevice, s));
-  PBF_HIP(hipMemcpyAsync(dabc.p, abc, 3 * n * 32, hipMemcpyHostToDevice, s));
-  PBF_HIP(hipMemcpyAsync(dsrs.p, srs, srs_m * 64, hipMemcpyHostToDevice, s));
-  PBF_HIP(hipMemcpyAsync(dpub.p, pub, npub * 32, hipMemcpyHostToDevice, s));
-  rc = pbf_plonk_prove_bn254_pi_dev(ctx, n, (const uint64_t*)dq.p, (const uint64_t*)dc.p, (const uint64_t*)dabc.p,
-                                    (const uint64_t*)dpub.p, npub, chal, rnd, k1k2, (const uint64_t*)dsrs.p, srs_m, mode,
-                                    out_pts, out_f, s);
-  if (rc) return rc;
-  PBF_HIP(hipStreamSynchronize(s));
-  return 0;
+  return prove_host_pub(ctx, n, q, copies, abc, pub, npub, chal, nullptr, rnd, k1k2, srs, srs_m, mode, out_pts, out_f,
+                        nullptr);
+}
+
+// Fiat-Shamir (pbf.h): the circuit digest in place of chal; out_chal null, or 6 x 4
+extern "C" int pbf_plonk_prove_bn254_fs_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
+                                            const uint64_t* d_abc, const uint64_t* d_pub, size_t npub,
+                                            const uint8_t* digest, const uint64_t* rnd, const uint64_t* k1k2,
+                                            const uint64_t* d_srs, size_t srs_m, int mode, uint64_t* out_pts,
+                                            uint64_t* out_f, uint64_t* out_chal, void* stream) {
+  if (!digest) return fail(PBF_EINVAL, "null argument");
+  return prove_impl(ctx, nullptr, n, d_q, d_copies, d_abc, nullptr, rnd, k1k2, d_srs, srs_m, mode, out_pts, out_f, stream,
+                    d_pub, npub, digest, out_chal);
+}
+
+extern "C" int pbf_plonk_prove_bn254_fs(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies,
+                                        const uint64_t* abc, const uint64_t* pub, size_t npub, const uint8_t* digest,
+                                        const uint64_t* rnd, const uint64_t* k1k2, const uint64_t* srs, size_t srs_m,
+                                        int mode, uint64_t* out_pts, uint64_t* out_f, uint64_t* out_chal) {
+  if (!digest) return fail(PBF_EINVAL, "null argument");
+  return prove_host_pub(ctx, n, q, copies, abc, pub, npub, nullptr, digest, rnd, k1k2, srs, srs_m, mode, out_pts, out_f,
+                        out_chal);
 }
 
 // ---------------------------------------------------------------- synthetic config-5 inputs

@@ -9,6 +9,7 @@
 #include "../../include/pbf.h"
 #include "plonk_terms.hpp"
 #include "prover.hpp"
+#include "transcript.hpp"
 
 using namespace pbf;
 
@@ -22,14 +23,17 @@ static int verify_with_vk(pbf_ctx* ctx, const PlonkDomain& dom, const uint64_t (
 // scalar (rand[0], plonk.rs:519). mode 0 keeps step 7's t_z (plonk.rs:575-581, no alpha on
 // the permutation term), mode 1 the paper's. *ok = 1 iff e(E1, [s]G2) == e(E2, G2).
 // pub, npub: the public inputs of pbf_plonk_verify_bn254_pi* (host; none: null, 0)
+// fs (pbf_plonk_verify_bn254_fs*): chal and u_in are null; the five challenges and u come from the
+// transcript (transcript.hpp) of the key's circuit digest, pub and the proof, derived on the host
 static int verify_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies, const uint64_t* d_srs,
                       size_t srs_m, const uint64_t* g2, const uint64_t* proof_pts, const uint64_t* proof_f,
                       const uint64_t* pub, size_t npub, const uint64_t* chal, const uint64_t* u_in, const uint64_t* k1k2,
-                      int mode, int* ok, void* stream) {
+                      int mode, int* ok, void* stream, bool fs = false) {
   int rc;
-  if ((rc = verifier_shape({ctx, d_q, d_copies, d_srs, g2, proof_pts, proof_f, chal, u_in, k1k2}, n, srs_m, ok)) ||
+  if ((rc = verifier_shape({ctx, d_q, d_copies, d_srs, g2, proof_pts, proof_f, k1k2}, n, srs_m, ok)) ||
       (rc = plonk_pub_validate(n, pub, npub, 1)))
     return rc;
+  if (!fs && (!chal || !u_in)) return fail(PBF_EINVAL, "null argument");
   PBF_HIP(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
   // Step 1-2: proof points on the curve, proof fields canonical (plonk.rs:523-547)
@@ -40,6 +44,15 @@ static int verify_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_
   const PlonkDomain dom = plonk_domain(n);
   uint64_t pre[8][8];
   if ((rc = verifier_vk(ctx, n, dom.omega, d_q, d_copies, d_srs, srs_m, k1k2, s, pre))) return rc;
+  uint64_t fs_chal[24];  // alpha beta gamma z v, u
+  if (fs) {
+    uint64_t h0[4], P[4], t6[4];
+    fs_circuit_digest(mode, n, npub, k1k2, pre, g2, h0);
+    fs_tree_digest_host(FS_TAG_PUB, pub, npub, P);
+    fs_proof_chain(h0, P, proof_pts, proof_f, fs_chal, fs_chal + 20, t6);
+    chal = fs_chal;
+    u_in = fs_chal + 20;
+  }
   // public inputs: sum_j pub_j w^j / (z - w^j) as a fraction (N, D), from the batched verifier's
   // kernels with count = 1
   uint64_t nd[8];  // Montgomery form as stored
@@ -186,18 +199,45 @@ extern "C" int pbf_plonk_verify_bn254(pbf_ctx* ctx, size_t n, const uint64_t* q,
                                    ok);
 }
 
+// the host forms: every argument error before the uploads
+static int verify_host(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies, const uint64_t* srs,
+                       size_t srs_m, const uint64_t* g2, const uint64_t* proof_pts, const uint64_t* proof_f,
+                       const uint64_t* pub, size_t npub, const uint64_t* chal, const uint64_t* u, const uint64_t* k1k2,
+                       int mode, int* ok, bool fs) {
+  int rc;
+  if ((rc = verifier_shape({ctx, q, copies, srs, g2, proof_pts, proof_f, k1k2}, n, srs_m, ok)) ||
+      (rc = plonk_pub_validate(n, pub, npub, 1)))
+    return rc;
+  if (!fs && (!chal || !u)) return fail(PBF_EINVAL, "null argument");
+  PBF_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->host_stream();
+  const uint64_t *d_q, *d_copies, *d_srs;
+  if ((rc = verifier_upload(ctx, n, q, copies, srs, srs_m, s, &d_q, &d_copies, &d_srs))) return rc;
+  return verify_dev(ctx, n, d_q, d_copies, d_srs, srs_m, g2, proof_pts, proof_f, pub, npub, chal, u, k1k2, mode, ok, s,
+                    fs);
+}
+
 extern "C" int pbf_plonk_verify_bn254_pi(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies,
                                          const uint64_t* srs, size_t srs_m, const uint64_t* g2,
                                          const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* pub,
                                          size_t npub, const uint64_t* chal, const uint64_t* u, const uint64_t* k1k2,
                                          int mode, int* ok) {
-  int rc;  // every argument error before the uploads
-  if ((rc = verifier_shape({ctx, q, copies, srs, g2, proof_pts, proof_f, chal, u, k1k2}, n, srs_m, ok)) ||
-      (rc = plonk_pub_validate(n, pub, npub, 1)))
-    return rc;
-  PBF_HIP(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->host_stream();
-  const uint64_t *d_q, *d_copies, *d_srs;
-  if ((rc = verifier_upload(ctx, n, q, copies, srs, srs_m, s, &d_q, &d_copies, &d_srs))) return rc;
-  return verify_dev(ctx, n, d_q, d_copies, d_srs, srs_m, g2, proof_pts, proof_f, pub, npub, chal, u, k1k2, mode, ok, s);
+  return verify_host(ctx, n, q, copies, srs, srs_m, g2, proof_pts, proof_f, pub, npub, chal, u, k1k2, mode, ok, false);
+}
+
+// Fiat-Shamir (pbf.h): no chal, no u
+extern "C" int pbf_plonk_verify_bn254_fs(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies,
+                                         const uint64_t* srs, size_t srs_m, const uint64_t* g2,
+                                         const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* pub,
+                                         size_t npub, const uint64_t* k1k2, int mode, int* ok) {
+  return verify_host(ctx, n, q, copies, srs, srs_m, g2, proof_pts, proof_f, pub, npub, nullptr, nullptr, k1k2, mode, ok,
+                     true);
+}
+
+extern "C" int pbf_plonk_verify_bn254_fs_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
+                                             const uint64_t* d_srs, size_t srs_m, const uint64_t* g2,
+                                             const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* pub,
+                                             size_t npub, const uint64_t* k1k2, int mode, int* ok, void* stream) {
+  return verify_dev(ctx, n, d_q, d_copies, d_srs, srs_m, g2, proof_pts, proof_f, pub, npub, nullptr, nullptr, k1k2, mode,
+                    ok, stream, true);
 }

@@ -22,6 +22,8 @@
 //                 proof over its chunks; plonk_verifier_scalars folds D_i into its one inversion
 //   k_vb_colsum*  the 9 shared-base scalars of an index range [lo, hi): LDS tree per block,
 //                 second step across blocks (field addition is exact: any order, same limbs)
+// chal, u and rho reach the device by upload, or (the _fs entries) are written there by the
+// transcript's kernels (transcript.hip fs_batch_run) from the proofs and pub this unit uploads.
 // Every scalar is the canonical value the single verifier's run of the same formulas gives.
 // Localisation (ok_each) halves the index range, recomputing only the column sums, the two MSMs and
 // the pairing per range.
@@ -31,6 +33,7 @@
 #include "../../include/pbf.h"
 #include "plonk_terms.hpp"
 #include "prover.hpp"
+#include "transcript.hpp"
 
 using namespace pbf;
 
@@ -286,14 +289,16 @@ struct Batch {
 };
 
 // every argument error, before anything is enqueued. chal and u are taken as the single
-// verifier takes them (fr_host.hpp hm()): any 256-bit value, reduced mod r.
+// verifier takes them (fr_host.hpp hm()): any 256-bit value, reduced mod r. fs: the _fs entries,
+// whose chal, u and rho are null (the transcript's kernels write them on the device).
 int vb_validate(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies, const uint64_t* srs, size_t srs_m,
                 const uint64_t* g2, size_t count, const uint64_t* proof_pts, const uint64_t* proof_f,
-                const uint64_t* chal, const uint64_t* u, const uint64_t* rho, const uint64_t* k1k2, int* ok) {
-  int rc = verifier_shape({ctx, q, copies, srs, g2, proof_pts, proof_f, chal, u, rho, k1k2}, n, srs_m, ok);
+                const uint64_t* chal, const uint64_t* u, const uint64_t* rho, const uint64_t* k1k2, int* ok, bool fs) {
+  int rc = verifier_shape({ctx, q, copies, srs, g2, proof_pts, proof_f, k1k2}, n, srs_m, ok);
   if (rc) return rc;
+  if (!fs && (!chal || !u || !rho)) return fail(PBF_EINVAL, "null argument");
   if (count == 0 || count > ((size_t)1 << 20)) return fail(PBF_EINVAL, "count must be in 1 .. 2^20");
-  for (size_t i = 0; i < count; ++i) {
+  for (size_t i = 0; !fs && i < count; ++i) {
     const uint64_t* r = rho + 4 * i;
     if (!fr_canonical(r) || !(r[0] | r[1] | r[2] | r[3])) return fail(PBF_EINVAL, "rho must be canonical and nonzero");
   }
@@ -343,10 +348,10 @@ int pbf::plonk_pub_validate(size_t n, const uint64_t* pub, size_t npub, size_t c
 static int vb_run(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies, const uint64_t* d_srs,
                   size_t srs_m, const uint64_t* g2, size_t count, const uint64_t* proof_pts, const uint64_t* proof_f,
                   const uint64_t* pub, size_t npub, const uint64_t* chal, const uint64_t* u, const uint64_t* rho,
-                  const uint64_t* k1k2, int mode, int* ok, int* ok_each, void* stream) {
+                  const uint64_t* k1k2, int mode, int* ok, int* ok_each, void* stream, bool fs = false) {
   int rc;
-  if ((rc = vb_validate(ctx, n, d_q, d_copies, d_srs, srs_m, g2, count, proof_pts, proof_f, chal, u, rho, k1k2, ok)) ||
-      (rc = plonk_pub_validate(n, pub, npub, count)))
+  if ((rc = vb_validate(ctx, n, d_q, d_copies, d_srs, srs_m, g2, count, proof_pts, proof_f, chal, u, rho, k1k2, ok, fs)) ||
+      (rc = plonk_pub_validate(n, pub, npub, count)) || (fs && (rc = fs_batch_validate(count, npub))))
     return rc;
   PBF_HIP(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
@@ -369,18 +374,29 @@ static int vb_run(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d
   PBF_HIP(hipMemcpyAsync(pts + 72 * c, &pre[0][0], 8 * 64, hipMemcpyHostToDevice, s));
   PBF_HIP(hipMemcpyAsync(pts + 72 * c + 64, d_srs, 64, hipMemcpyDeviceToDevice, s));
   PBF_HIP(hipMemcpyAsync(bf.p, proof_f, 7 * c * 32, hipMemcpyHostToDevice, s));
-  PBF_HIP(hipMemcpyAsync(bc.p, chal, 5 * c * 32, hipMemcpyHostToDevice, s));
-  PBF_HIP(hipMemcpyAsync(bu.p, u, c * 32, hipMemcpyHostToDevice, s));
-  PBF_HIP(hipMemcpyAsync(br.p, rho, c * 32, hipMemcpyHostToDevice, s));
+  DevBuf& bpub = ctx->buf("vb.pub");  // read by the transcript (fs) and by the public-input sums below
+  if ((rc = bpub.ensure(c * npub * 32))) return rc;
+  if (npub) PBF_HIP(hipMemcpyAsync(bpub.p, pub, c * npub * 32, hipMemcpyHostToDevice, s));
+  if (fs) {  // chal, u, rho from the transcript of the proofs and pub just uploaded, never through the host
+    uint64_t h0[4];
+    fs_circuit_digest(mode, n, npub, k1k2, pre, g2, h0);
+    if ((rc = fs_batch_run(ctx, h0, c, (const uint64_t*)pts, (const uint64_t*)bf.p,
+                           npub ? (const uint64_t*)bpub.p : nullptr, npub, (uint64_t*)bc.p, (uint64_t*)bu.p,
+                           (uint64_t*)br.p, s)))
+      return rc;
+  } else {
+    PBF_HIP(hipMemcpyAsync(bc.p, chal, 5 * c * 32, hipMemcpyHostToDevice, s));
+    PBF_HIP(hipMemcpyAsync(bu.p, u, c * 32, hipMemcpyHostToDevice, s));
+    PBF_HIP(hipMemcpyAsync(br.p, rho, c * 32, hipMemcpyHostToDevice, s));
+  }
   PBF_HIP(hipMemsetAsync(bfl.p, 0, c * sizeof(int), s));
   const VbParams P{hm(k1k2), hm(k1k2 + 4), dom, (uint32_t)c, mode};
   const uint32_t npts = (uint32_t)(9 * c);
   hipLaunchKernelGGL(k_vb_curve, dim3((npts + 255) / 256), dim3(256), 0, s, (const uint64_t*)pts, npts, (int*)bfl.p,
                      (uint64_t*)bq.p);
   if (npub) {  // once per call: localisation reuses the per-proof scalars
-    DevBuf &bpub = ctx->buf("vb.pub"), &bnd = ctx->buf("vb.pind");
-    if ((rc = bpub.ensure(c * npub * 32)) || (rc = bnd.ensure(c * 64))) return rc;
-    PBF_HIP(hipMemcpyAsync(bpub.p, pub, c * npub * 32, hipMemcpyHostToDevice, s));
+    DevBuf& bnd = ctx->buf("vb.pind");
+    if ((rc = bnd.ensure(c * 64))) return rc;
     if ((rc = plonk_pi_fraction_run(ctx, dom.omega, (const uint64_t*)bpub.p, npub, (const uint64_t*)bc.p, c,
                                     (uint64_t*)bnd.p, s)))
       return rc;
@@ -410,6 +426,23 @@ static int vb_run(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d
   bool left = false, right = false;
   if ((rc = B.localise(0, mid, false, &left))) return rc;
   return B.localise(mid, c, left, &right);
+}
+
+// the host forms: every argument error before the uploads
+static int vb_host(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies, const uint64_t* srs, size_t srs_m,
+                   const uint64_t* g2, size_t count, const uint64_t* proof_pts, const uint64_t* proof_f,
+                   const uint64_t* pub, size_t npub, const uint64_t* chal, const uint64_t* u, const uint64_t* rho,
+                   const uint64_t* k1k2, int mode, int* ok, int* ok_each, bool fs) {
+  int rc;
+  if ((rc = vb_validate(ctx, n, q, copies, srs, srs_m, g2, count, proof_pts, proof_f, chal, u, rho, k1k2, ok, fs)) ||
+      (rc = plonk_pub_validate(n, pub, npub, count)))
+    return rc;
+  PBF_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->host_stream();
+  const uint64_t *d_q, *d_copies, *d_srs;
+  if ((rc = verifier_upload(ctx, n, q, copies, srs, srs_m, s, &d_q, &d_copies, &d_srs))) return rc;
+  return vb_run(ctx, n, d_q, d_copies, d_srs, srs_m, g2, count, proof_pts, proof_f, pub, npub, chal, u, rho, k1k2, mode, ok,
+                ok_each, s, fs);
 }
 
 extern "C" int pbf_plonk_verify_bn254_batch_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
@@ -445,14 +478,24 @@ extern "C" int pbf_plonk_verify_bn254_batch_pi(pbf_ctx* ctx, size_t n, const uin
                                                const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* pub,
                                                size_t npub, const uint64_t* chal, const uint64_t* u, const uint64_t* rho,
                                                const uint64_t* k1k2, int mode, int* ok, int* ok_each) {
-  int rc;
-  if ((rc = vb_validate(ctx, n, q, copies, srs, srs_m, g2, count, proof_pts, proof_f, chal, u, rho, k1k2, ok)) ||
-      (rc = plonk_pub_validate(n, pub, npub, count)))
-    return rc;
-  PBF_HIP(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->host_stream();
-  const uint64_t *d_q, *d_copies, *d_srs;
-  if ((rc = verifier_upload(ctx, n, q, copies, srs, srs_m, s, &d_q, &d_copies, &d_srs))) return rc;
-  return vb_run(ctx, n, d_q, d_copies, d_srs, srs_m, g2, count, proof_pts, proof_f, pub, npub, chal, u, rho, k1k2, mode, ok,
-                ok_each, s);
+  return vb_host(ctx, n, q, copies, srs, srs_m, g2, count, proof_pts, proof_f, pub, npub, chal, u, rho, k1k2, mode, ok,
+                 ok_each, false);
+}
+
+// Fiat-Shamir (pbf.h): no chal, no u, no rho
+extern "C" int pbf_plonk_verify_bn254_batch_fs(pbf_ctx* ctx, size_t n, const uint64_t* q, const uint64_t* copies,
+                                               const uint64_t* srs, size_t srs_m, const uint64_t* g2, size_t count,
+                                               const uint64_t* proof_pts, const uint64_t* proof_f, const uint64_t* pub,
+                                               size_t npub, const uint64_t* k1k2, int mode, int* ok, int* ok_each) {
+  return vb_host(ctx, n, q, copies, srs, srs_m, g2, count, proof_pts, proof_f, pub, npub, nullptr, nullptr, nullptr, k1k2,
+                 mode, ok, ok_each, true);
+}
+
+extern "C" int pbf_plonk_verify_bn254_batch_fs_dev(pbf_ctx* ctx, size_t n, const uint64_t* d_q, const uint64_t* d_copies,
+                                                   const uint64_t* d_srs, size_t srs_m, const uint64_t* g2, size_t count,
+                                                   const uint64_t* proof_pts, const uint64_t* proof_f,
+                                                   const uint64_t* pub, size_t npub, const uint64_t* k1k2, int mode,
+                                                   int* ok, int* ok_each, void* stream) {
+  return vb_run(ctx, n, d_q, d_copies, d_srs, srs_m, g2, count, proof_pts, proof_f, pub, npub, nullptr, nullptr, nullptr,
+                k1k2, mode, ok, ok_each, stream, true);
 }

@@ -35,6 +35,8 @@ _p64 = ctypes.POINTER(ctypes.c_uint64)
 _sz = ctypes.c_size_t
 _vp = ctypes.c_void_p
 _p32 = ctypes.POINTER(ctypes.c_uint32)
+_p8 = ctypes.POINTER(ctypes.c_uint8)
+_pint = ctypes.POINTER(ctypes.c_int)
 
 # (name, restype, argtypes) for every entry point in include/pbf.h
 SIGNATURES = [
@@ -102,6 +104,25 @@ SIGNATURES = [
                                                            _sz, _p64, _p64, _p64, _p64, ctypes.c_int,
                                                            ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                                            _vp]),
+    ("pbf_keccak256_batch", ctypes.c_int, [_vp, _p8, _sz, _sz, _sz, _p8]),
+    ("pbf_keccak256_batch_dev", ctypes.c_int, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
+    ("pbf_plonk_circuit_digest_bn254", ctypes.c_int, [_vp, _sz, _p64, _p64, _p64, _sz, _p64, _p64, ctypes.c_int, _sz,
+                                                      _p8]),
+    ("pbf_plonk_circuit_digest_bn254_dev", ctypes.c_int, [_vp, _sz, _vp, _vp, _vp, _sz, _p64, _p64, ctypes.c_int, _sz,
+                                                          _p8, _vp]),
+    ("pbf_plonk_challenges_bn254", ctypes.c_int, [_vp, _p8, _sz, _p64, _p64, _p64, _sz, _p64, _p64, _p64]),
+    ("pbf_plonk_prove_bn254_fs", ctypes.c_int, [_vp, _sz, _p64, _p64, _p64, _p64, _sz, _p8, _p64, _p64, _p64, _sz,
+                                                ctypes.c_int, _p64, _p64, _p64]),
+    ("pbf_plonk_prove_bn254_fs_dev", ctypes.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, _sz, _p8, _p64, _p64, _vp, _sz,
+                                                    ctypes.c_int, _p64, _p64, _p64, _vp]),
+    ("pbf_plonk_verify_bn254_fs", ctypes.c_int, [_vp, _sz, _p64, _p64, _p64, _sz, _p64, _p64, _p64, _p64, _sz, _p64,
+                                                 ctypes.c_int, _pint]),
+    ("pbf_plonk_verify_bn254_fs_dev", ctypes.c_int, [_vp, _sz, _vp, _vp, _vp, _sz, _p64, _p64, _p64, _p64, _sz, _p64,
+                                                     ctypes.c_int, _pint, _vp]),
+    ("pbf_plonk_verify_bn254_batch_fs", ctypes.c_int, [_vp, _sz, _p64, _p64, _p64, _sz, _p64, _sz, _p64, _p64, _p64,
+                                                       _sz, _p64, ctypes.c_int, _pint, _pint]),
+    ("pbf_plonk_verify_bn254_batch_fs_dev", ctypes.c_int, [_vp, _sz, _vp, _vp, _vp, _sz, _p64, _sz, _p64, _p64, _p64,
+                                                           _sz, _p64, ctypes.c_int, _pint, _pint, _vp]),
     ("pbf_plonk_prove_bn254_sharded_dev", ctypes.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _p64, _p64, _p64, _vp, _sz,
                                                          ctypes.c_int, _p64, _p64, _vp]),
     ("pbf_plonk_synth_circuit_bn254_dev", ctypes.c_int, [_vp, _sz, _u64, _vp, _vp, _vp, _vp]),
@@ -618,6 +639,150 @@ class Context:
                                                             _ptr(pb) if npub else None, npub, _ptr(cha), _ptr(ua),
                                                             _ptr(ra), _ptr(ints_to_limbs(k1k2)), mode,
                                                             ctypes.byref(ok), oe, stream))
+        return (ok.value == 1, [bool(v) for v in oe[:count]]) if each else ok.value == 1
+
+    # ---- Fiat-Shamir (include/pbf.h "Fiat-Shamir"; transcript.hip): digests are 32 bytes
+    @staticmethod
+    def _digest_arg(digest):
+        a = np.frombuffer(bytes(digest), dtype=np.uint8).copy()
+        if a.size != 32:
+            raise ValueError("a circuit digest is 32 bytes")
+        return a
+
+    def keccak256_batch(self, msgs, pitch: int | None = None) -> list:
+        """Keccak-256 of byte strings of one length, laid out `pitch` bytes apart (default: compact)."""
+        count, ln = len(msgs), (len(msgs[0]) if msgs else 0)
+        if any(len(m) != ln for m in msgs):
+            raise ValueError("every message of a batch has the same length")
+        pitch = ln if pitch is None else pitch
+        buf = np.zeros(max(count * max(pitch, ln), 1), dtype=np.uint8)
+        for i, m in enumerate(msgs):
+            buf[i * pitch:i * pitch + ln] = np.frombuffer(bytes(m), dtype=np.uint8)
+        out = np.zeros(max(count, 1) * 32, dtype=np.uint8)
+        _check(self.lib.pbf_keccak256_batch(self.h, buf.ctypes.data_as(_p8), count, ln, pitch, out.ctypes.data_as(_p8)))
+        return [out[32 * i:32 * i + 32].tobytes() for i in range(count)]
+
+    def keccak256_batch_dev(self, d_msgs: int, count: int, length: int, pitch: int, d_out: int, stream: int = 0):
+        _check(self.lib.pbf_keccak256_batch_dev(self.h, d_msgs, count, length, pitch, d_out, stream))
+
+    def plonk_circuit_digest_bn254(self, q, copies, srs, g2s, npub: int, k1k2=(2, 3), mode=0) -> bytes:
+        """h0 of the transcript: the circuit's verification key, k1 k2, mode, n, npub and [s]G2."""
+        n = len(q[0])
+        qa, ca, sa = _circuit_limbs(q, copies, srs)
+        out = np.zeros(32, dtype=np.uint8)
+        _check(self.lib.pbf_plonk_circuit_digest_bn254(self.h, n, _ptr(qa), _ptr(ca), _ptr(sa), len(srs),
+                                                       _ptr(_g2_limbs(g2s)), _ptr(ints_to_limbs(k1k2)), mode, npub,
+                                                       out.ctypes.data_as(_p8)))
+        return out.tobytes()
+
+    def plonk_circuit_digest_bn254_dev(self, n, d_q, d_copies, d_srs, srs_m, g2s, npub: int, k1k2=(2, 3), mode=0,
+                                       stream: int = 0) -> bytes:
+        out = np.zeros(32, dtype=np.uint8)
+        _check(self.lib.pbf_plonk_circuit_digest_bn254_dev(self.h, n, d_q, d_copies, d_srs, srs_m, _ptr(_g2_limbs(g2s)),
+                                                           _ptr(ints_to_limbs(k1k2)), mode, npub,
+                                                           out.ctypes.data_as(_p8), stream))
+        return out.tobytes()
+
+    def plonk_challenges_bn254(self, digest, proofs, pubs, rho: bool = True):
+        """The transcript's challenges of a batch: ([alpha beta gamma z v] per proof, [u], [rho] or
+        None). proofs: (pts, fields) pairs; pubs: one list of public inputs per proof."""
+        count, pa, fa, pb, npub = self._batch_fs_arrays(proofs, pubs)
+        d = self._digest_arg(digest)
+        ca = np.zeros(20 * max(count, 1), dtype=np.uint64)
+        ua = np.zeros(4 * max(count, 1), dtype=np.uint64)
+        ra = np.zeros(4 * max(count, 1), dtype=np.uint64) if rho else None
+        _check(self.lib.pbf_plonk_challenges_bn254(self.h, d.ctypes.data_as(_p8), count, _ptr(pa), _ptr(fa),
+                                                   _ptr(pb) if npub else None, npub, _ptr(ca), _ptr(ua),
+                                                   _ptr(ra) if rho else None))
+        cv = limbs_to_ints(ca)
+        return [cv[5 * i:5 * i + 5] for i in range(count)], limbs_to_ints(ua)[:count], \
+            (limbs_to_ints(ra)[:count] if rho else None)
+
+    def plonk_prove_bn254_fs(self, q, copies, abc, pub, digest, rnd, srs, k1k2=(2, 3), mode=0, npub=None):
+        """plonk_prove_bn254_pi with the challenges derived from the transcript under `digest`
+        (plonk_circuit_digest_bn254). Returns (9 points, 7 fields, [alpha beta gamma z v u])."""
+        n = len(abc[0])
+        qa, ca, aa, sa = _circuit_limbs(q, copies, srs, abc)
+        _keep, pp, npub = self._pub_arg(pub, npub)
+        d = self._digest_arg(digest)
+        pts = np.zeros(72, dtype=np.uint64)
+        fs = np.zeros(28, dtype=np.uint64)
+        ch = np.zeros(24, dtype=np.uint64)
+        _check(self.lib.pbf_plonk_prove_bn254_fs(self.h, n, _ptr(qa), _ptr(ca), _ptr(aa), pp, npub,
+                                                 d.ctypes.data_as(_p8), _ptr(ints_to_limbs(rnd)),
+                                                 _ptr(ints_to_limbs(k1k2)), _ptr(sa), len(srs), mode, _ptr(pts), _ptr(fs),
+                                                 _ptr(ch)))
+        pv = limbs_to_ints(pts)
+        return [None if pv[2 * i] == 0 and pv[2 * i + 1] == 0 else (pv[2 * i], pv[2 * i + 1]) for i in range(9)], \
+            limbs_to_ints(fs), limbs_to_ints(ch)
+
+    def plonk_prove_bn254_fs_dev(self, n, d_q, d_copies, d_abc, d_pub, npub, digest, rnd, d_srs, srs_m, k1k2=(2, 3),
+                                 mode=0, stream: int = 0):
+        """The same on device inputs; returns (pts limbs, field limbs, challenge limbs 6 x 4)."""
+        d = self._digest_arg(digest)
+        pts = np.zeros(72, dtype=np.uint64)
+        fs = np.zeros(28, dtype=np.uint64)
+        ch = np.zeros(24, dtype=np.uint64)
+        _check(self.lib.pbf_plonk_prove_bn254_fs_dev(self.h, n, d_q, d_copies, d_abc, d_pub or None, npub,
+                                                     d.ctypes.data_as(_p8), _ptr(ints_to_limbs(rnd)),
+                                                     _ptr(ints_to_limbs(k1k2)), d_srs, srs_m, mode, _ptr(pts), _ptr(fs),
+                                                     _ptr(ch), stream))
+        return pts, fs, ch
+
+    def plonk_verify_bn254_fs(self, q, copies, srs, g2s, pts, fields, pub, k1k2=(2, 3), mode=0, npub=None) -> bool:
+        n = len(q[0])
+        qa, ca, sa = _circuit_limbs(q, copies, srs)
+        pa, fa = _proof_limbs(pts, fields)
+        _keep, pp, npub = self._pub_arg(pub, npub)
+        ok = ctypes.c_int(-1)
+        _check(self.lib.pbf_plonk_verify_bn254_fs(self.h, n, _ptr(qa), _ptr(ca), _ptr(sa), len(srs),
+                                                  _ptr(_g2_limbs(g2s)), _ptr(pa), _ptr(fa), pp, npub,
+                                                  _ptr(ints_to_limbs(k1k2)), mode, ctypes.byref(ok)))
+        return ok.value == 1
+
+    def plonk_verify_bn254_fs_dev(self, n, d_q, d_copies, d_srs, srs_m, g2s, pts, fields, pub, k1k2=(2, 3), mode=0,
+                                  stream: int = 0, npub=None) -> bool:
+        pa, fa = _proof_limbs(pts, fields)
+        _keep, pp, npub = self._pub_arg(pub, npub)
+        ok = ctypes.c_int(-1)
+        _check(self.lib.pbf_plonk_verify_bn254_fs_dev(self.h, n, d_q, d_copies, d_srs, srs_m, _ptr(_g2_limbs(g2s)),
+                                                      _ptr(pa), _ptr(fa), pp, npub, _ptr(ints_to_limbs(k1k2)), mode,
+                                                      ctypes.byref(ok), stream))
+        return ok.value == 1
+
+    def _batch_fs_arrays(self, proofs, pubs):
+        count = len(proofs)
+        pa = np.zeros(72 * max(count, 1), dtype=np.uint64)
+        fa = np.zeros(28 * max(count, 1), dtype=np.uint64)
+        for i, (pts, fields) in enumerate(proofs):
+            pa[72 * i:72 * i + 72], fa[28 * i:28 * i + 28] = _proof_limbs(pts, fields)
+        if len(pubs) != count:
+            raise ValueError("one list of public inputs per proof")
+        pb, npub = self._batch_pub(pubs)
+        return count, pa, fa, pb, npub
+
+    def plonk_verify_bn254_batch_fs(self, q, copies, srs, g2s, proofs, pubs, k1k2=(2, 3), mode=0, each=False):
+        """plonk_verify_bn254_batch_pi with chal, u and rho derived on the device from the transcript."""
+        n = len(q[0])
+        qa, ca, sa = _circuit_limbs(q, copies, srs)
+        count, pa, fa, pb, npub = self._batch_fs_arrays(proofs, pubs)
+        ok = ctypes.c_int(-1)
+        oe = (ctypes.c_int * max(count, 1))() if each else None
+        _check(self.lib.pbf_plonk_verify_bn254_batch_fs(self.h, n, _ptr(qa), _ptr(ca), _ptr(sa), len(srs),
+                                                        _ptr(_g2_limbs(g2s)), count, _ptr(pa), _ptr(fa),
+                                                        _ptr(pb) if npub else None, npub, _ptr(ints_to_limbs(k1k2)), mode,
+                                                        ctypes.byref(ok), oe))
+        return (ok.value == 1, [bool(v) for v in oe[:count]]) if each else ok.value == 1
+
+    def plonk_verify_bn254_batch_fs_dev(self, n, d_q, d_copies, d_srs, srs_m, g2s, proofs, pubs, k1k2=(2, 3), mode=0,
+                                        each=False, stream: int = 0):
+        count, pa, fa, pb, npub = self._batch_fs_arrays(proofs, pubs)
+        ok = ctypes.c_int(-1)
+        oe = (ctypes.c_int * max(count, 1))() if each else None
+        _check(self.lib.pbf_plonk_verify_bn254_batch_fs_dev(self.h, n, d_q, d_copies, d_srs, srs_m,
+                                                            _ptr(_g2_limbs(g2s)), count, _ptr(pa), _ptr(fa),
+                                                            _ptr(pb) if npub else None, npub, _ptr(ints_to_limbs(k1k2)),
+                                                            mode, ctypes.byref(ok), oe, stream))
         return (ok.value == 1, [bool(v) for v in oe[:count]]) if each else ok.value == 1
 
     # ---- KZG commitments over BN254 (include/pbf.h "KZG commitments"; kzg.hip)
