@@ -264,6 +264,30 @@ constexpr uint64_t GL_BLK_PITCH = 8192;
 static_assert(GL_BLK_PITCH >= 8192 && GL_BLK_PITCH % 2 == 0, "block pitch");
 typedef uint64_t gl_u64x2 __attribute__((ext_vector_type(2)));
 
+// The global accesses of SP 2: the address is a wave-uniform 64-bit base, which carries the
+// kernel's pointer, the polynomial, the tile and the stride of this access, plus one 32-bit byte
+// offset per lane that all accesses of a family share. The base stays in scalar registers and is
+// advanced by the scalar ALU (global_load / global_store with a scalar base and a 32-bit vector
+// offset): no access forms a 64-bit address on the vector ALU or keeps one live. The offset is
+// zero-extended, so every lane offset must stay below 2^32 bytes: here below one polynomial.
+// The empty asm pins the finished base to a scalar register pair: without it the compiler takes
+// the stride back out of the base, adds the lane offset first and the stride on the vector ALU.
+// (The pointer that comes out of the asm is one to global memory by its type, not by inference.)
+#define GL_GLOBAL __attribute__((address_space(1)))
+template <class T>
+__device__ __forceinline__ T gl_ld_sv(const void* sbase, uint32_t voff) {
+  uint64_t b = (uint64_t)sbase;
+  asm("" : "+s"(b));
+  return *(const GL_GLOBAL T*)((const GL_GLOBAL char*)b + voff);
+}
+template <class T>
+__device__ __forceinline__ void gl_st_sv(void* sbase, uint32_t voff, T x) {
+  uint64_t b = (uint64_t)sbase;
+  asm("" : "+s"(b));
+  *(GL_GLOBAL T*)((GL_GLOBAL char*)b + voff) = x;
+}
+#undef GL_GLOBAL
+
 // One tile: stages A, B, C and the stores.
 // RG (regrouped 2^24 plan, ntt_gl_rg2_kernel below): 1 = its first pass, 3 = its last pass.
 // CS (coset transforms): 1 = a first pass that scales its loads by shift^i and reads no zero
@@ -311,10 +335,11 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
     // (u' < 8), i.e. rows r = 128 u' + (t >> 2) = 256 s1 + 16 s2 + r2 with s1 = u' >> 1,
     // s2 = 8 (u' & 1) + (t >> 6), r2 = (t >> 2) & 15, and columns w = 2 (t & 3) + b: v[(2h + b)*4
     // + s1], h = u' & 1, so that each group of four shares (s2, r2, w) like the natural mapping
-    const gl_u64x2* blk = (const gl_u64x2*)(in + (uint64_t)kb * a.blk_pitch) + t;
+    const gl_u64x2* blk = (const gl_u64x2*)(in + (uint64_t)kb * a.blk_pitch);  // wave-uniform
+    const uint32_t lane_off = (uint32_t)t * 16;
 #pragma unroll
     for (int up = 0; up < 8; ++up) {
-      const gl_u64x2 e = blk[512 * up];
+      const gl_u64x2 e = gl_ld_sv<gl_u64x2>(blk + 512 * up, lane_off);
       v[(2 * (up & 1)) * 4 + (up >> 1)] = e.x;
       v[(2 * (up & 1) + 1) * 4 + (up >> 1)] = e.y;
     }
@@ -338,6 +363,18 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
       }
 #pragma unroll
       for (int m = 0; m < 8; ++m) v[8 * h + m] = G::mul(v[8 * h + m], tw[m], f);
+    }
+  } else if constexpr (SP == 2) {
+    // the natural mapping below with n = R^2 (rows R long): row r = 16 C s1 + NT / W u + t / W,
+    // so the lane's part (t / W, t % W) is one offset and (s1, u) a wave-uniform stride
+    static_assert(NT / W == 4 * C && 4 * (NT / W) == 16 * C, "rows of one load: 16 C s1 + 4 C u + t / W");
+    const uint64_t* row0 = in + j0;
+    const uint32_t lane_off = ((uint32_t)(t / W) << LOGR | (uint32_t)(t % W)) * 8;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+#pragma unroll
+      for (int s1 = 0; s1 < 4; ++s1)
+        v[u * 4 + s1] = gl_ld_sv<uint64_t>(row0 + ((uint64_t)(16 * C * s1 + (NT / W) * u) << LOGR), lane_off);
     }
   } else {
 #pragma unroll
@@ -619,16 +656,16 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
     // the lane
     static_assert(Sh::NSUB_C == 1 && W == 8, "tile-major stores: one sub-DFT per thread");
     const uint64_t base = (uint64_t)__builtin_amdgcn_readfirstlane(tc >> 6) * a.blk_pitch + j0 * W;
-    const uint32_t lane = tc & 63;
+    const uint32_t lane_off = (tc & 63) * 8;
     const uint64_t* ptw = a.post_tw + base;
     uint64_t* o = a.out + (uint64_t)poly * a.out_pitch + base;
     uint64_t tw[C];
 #pragma unroll
-    for (int k2 = 0; k2 < C; ++k2) tw[k2] = ptw[(uint64_t)(8 * k2) * a.blk_pitch + lane];
+    for (int k2 = 0; k2 < C; ++k2) tw[k2] = gl_ld_sv<uint64_t>(ptw + (uint64_t)(8 * k2) * a.blk_pitch, lane_off);
 #pragma unroll
     for (int k2 = 0; k2 < C; ++k2) x[bitrev_c(k2, LOGC)] = G::mul(x[bitrev_c(k2, LOGC)], tw[k2], f);
 #pragma unroll
-    for (int k2 = 0; k2 < C; ++k2) o[(uint64_t)(8 * k2) * a.blk_pitch + lane] = x[bitrev_c(k2, LOGC)];
+    for (int k2 = 0; k2 < C; ++k2) gl_st_sv<uint64_t>(o + (uint64_t)(8 * k2) * a.blk_pitch, lane_off, x[bitrev_c(k2, LOGC)]);
   } else if constexpr (FIRST) {
     uint64_t* o = a.out + (uint64_t)poly * a.out_pitch;
 #pragma unroll
@@ -646,8 +683,17 @@ __device__ __forceinline__ void gl_tile(const GlPassArgs& a, uint64_t* lds, uint
 #pragma unroll
       for (int k2 = 0; k2 < C; ++k2) o[base + k1 + 64 * k2] = x[u * C + bitrev_c(k2, LOGC)];
     }
+  } else if constexpr (SP == 2) {
+    // the natural-order store below with log_ns = LOGR and the tile's W columns inside one run
+    // (j0 a multiple of W): out[(j0 >> LOGR << 2 LOGR) + (j0 mod R) + w + (k1 + 64 k2 << LOGR)],
+    // (k1, w) the lane's offset, j0 and k2 wave-uniform
+    static_assert(Sh::NSUB_C == 1 && (1 << LOGR) % W == 0, "one sub-DFT per thread, whole runs");
+    uint64_t* o = a.out + (uint64_t)poly * a.out_pitch + ((j0 >> LOGR) << (2 * LOGR)) + (j0 & ((1u << LOGR) - 1));
+    const uint32_t lane_off = ((uint32_t)(tc / W) << LOGR | (uint32_t)(tc % W)) * 8;
+#pragma unroll
+    for (int k2 = 0; k2 < C; ++k2) gl_st_sv<uint64_t>(o + ((uint64_t)(64 * k2) << LOGR), lane_off, x[bitrev_c(k2, LOGC)]);
   } else {
-    const uint32_t lns = SP == 2 ? (uint32_t)LOGR : a.log_ns;
+    const uint32_t lns = a.log_ns;
     const uint64_t ns_mask = (1ull << lns) - 1;
     uint64_t* out = a.out + (uint64_t)poly * a.out_pitch;
     const uint32_t sl = SP != 0 ? 0u : a.out_split_log;
